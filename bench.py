@@ -12,13 +12,18 @@ before any HIP call: launch_ranks), `python -m torch.distributed.run ... bench.p
 results are all-gathered over RCCL/xGMI.  A line labelled n_gpus: N is N ranks on N
 devices -- fewer devices than ranks is refused unless --share-devices (a test mode).
 
-value = (L-BFGS iterations of the whole job) * N * M / wall-clock, max over ranks.
+value = (L-BFGS iterations of the whole job) * N * M / wall-clock, max over ranks; ms_per_step = wall-clock of one
+timed sweep.  A plain run does only that: set up, warm up, time --steps sweeps, print the line.  --full adds every
+side record and the roofline figures that take runs of their own (read ceiling, live PMC traffic); --dump-outputs DIR
+writes what the last timed sweep returned (dump_outputs).
 
 --method forces runs BASELINE.json configs[4] instead (forces method, N = 1e6 x M = 512, the theta series as one
 lock-step batch; with --gpus N the structures are split over the ranks, two small all-gathers per evaluation).
 
     python bench.py                      # 1 GPU, 1 warm-up + 1 timed sweep
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs out    # + out/*.npy of the last timed sweep
+    python bench.py --full               # + the side records (about 5 minutes)
     python bench.py --gpus 8             # 8 ranks started by this script
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
            --master-port 29511 bench.py --gpus 8 --steps 1 --warmup 1
@@ -979,6 +984,21 @@ def api_record(bioen_amd, yTilde, YTilde, thetas, label, with_unheld):
     return rec
 
 
+def dump_outputs(directory, results, seed=SEED):
+    """--dump-outputs: what a caller of the timed path received from its last sweep, as float64 .npy files, so that two
+    builds can be compared output for output -- per theta (in the sweep's order) theta, fmin, chi2, S, iterations,
+    evaluations and code, and the weights w on a fixed, seeded sample of the structures (all of them for N <= 2^19;
+    `w_index` = the sampled columns).  Under 64 MB in all: 9 x 2^19 x 8 B = 38 MB at the headline's 8 thetas."""
+    os.makedirs(directory, exist_ok=True)
+    for key in ("theta", "fmin", "chi2", "S", "iterations", "evaluations", "code"):
+        np.save(os.path.join(directory, key + ".npy"), np.array([r[key] for r in results], dtype=np.float64))
+    n, k = results[0]["w"].size, len(results)
+    size = min(n, 1 << 19, 7000000 // (k + 1))
+    idx = np.arange(n) if size == n else np.sort(np.random.default_rng(seed).choice(n, size=size, replace=False))
+    np.save(os.path.join(directory, "w_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(directory, "w.npy"), np.stack([np.asarray(r["w"], dtype=np.float64)[idx] for r in results]))
+
+
 class stdout_to_stderr(object):
     """librccl prints a version banner on stdout when a communicator is created; keep this
     process' stdout for the ONE JSON line."""
@@ -1252,10 +1272,23 @@ def main():
     ap.add_argument("--budget", type=float, default=260.0,
                     help="wall budget in seconds for the SIDE records after the timed region; they are dropped lowest priority "
                          "first with \"skipped\": \"budget\" -- roofline and cpu_baseline are never dropped")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline: the side records (CPU baselines, forces, DEER, ala5, API, one-copy, "
+                         "storage), the read ceiling and live PMC traffic of the roofline, the multi-rank final gather; the --no-* "
+                         "switches thin out a --full run.  Without it a run sets up, warms up, times --steps sweeps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed sweep returned as float64 DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if not args.full:
+        # a plain run does only what its headline needs: every side record and every figure that takes runs of its own is off
+        for k in list(vars(args)):
+            if k.startswith("no_"):
+                setattr(args, k, True)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # r06: no launcher around us -- become it.  Nothing below this branch runs in this process: no HIP call, no
         # bioen_amd import; the N children re-enter main() with the rank environment set.
@@ -1407,7 +1440,7 @@ def main():
     # theta-dealing runs have gathered through RCCL inside it (sweep.theta_sweep) and are checked the same way.  A failure
     # is reported in the line, never fatal.
     final_gather = None
-    if world > 1:
+    if world > 1 and args.full:
         # only the gather itself may fail on a rank; the two control-plane collectives behind it run on EVERY rank whatever
         # happened, so that no rank waits in them for one that left through the except branch
         try:
@@ -1426,6 +1459,9 @@ def main():
     evals_per_sweep = sum(r["evaluations"] for r in results)
     total_iters = iters_per_sweep * args.steps
     value = total_iters * float(N) * M / dt
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, results)
 
     if rank == 0:
         # ---- roofline of the dominant (slower) matrix-streaming kernel, rank 0's launches ----
@@ -1472,13 +1508,14 @@ def main():
                     "traffic_source": "profiles/traffic.json (builder's rocprofv3 --pmc passes of these kernel sources)"
                                       if traffic is not None else None}
 
-        try:      # what this box's memory system gives a plain read-only stream over the same copy of the matrix
-            ceil_gbs, ceil_bytes = ctx.read_probe(reps=10)
-            roofline["read_ceiling"] = {"GB/s": ceil_gbs, "bytes_per_pass": ceil_bytes, "frac_of_peak": ceil_gbs / HBM_PEAK_GBS,
-                                        "kernel": "k_read_probe: wide nontemporal loads and an add, no LDS, no matrix cores",
-                                        "achieved_over_ceiling": roofline["achieved"] / ceil_gbs}
-        except Exception as e:
-            roofline["read_ceiling"] = {"error": repr(e)}
+        if args.full:
+            try:      # what this box's memory system gives a plain read-only stream over the same copy of the matrix
+                ceil_gbs, ceil_bytes = ctx.read_probe(reps=10)
+                roofline["read_ceiling"] = {"GB/s": ceil_gbs, "bytes_per_pass": ceil_bytes, "frac_of_peak": ceil_gbs / HBM_PEAK_GBS,
+                                            "kernel": "k_read_probe: wide nontemporal loads and an add, no LDS, no matrix cores",
+                                            "achieved_over_ceiling": roofline["achieved"] / ceil_gbs}
+            except Exception as e:
+                roofline["read_ceiling"] = {"error": repr(e)}
 
         # ---- side records, under a wall budget (r06) -------------------------------------------------------------
         # Everything below is reported BESIDE the headline; the driver's clock runs on.  `--budget` seconds (default 260)
@@ -1712,6 +1749,9 @@ def main():
                            "evaluations": r["evaluations"], "code": r["code"], "fmin": r["fmin"],
                            "chi2": r["chi2"], "S": r["S"], "seconds": r["seconds"]} for r in results],
         }
+        if not args.full:      # none of the side records ran: they are --full's
+            for k in ("cpu_baseline", "forces", "storage_experiment", "one_copy", "api_end_to_end", "deer", "ala5", "side_records"):
+                del line[k]
         print(json.dumps(line))
         sys.stdout.flush()
 

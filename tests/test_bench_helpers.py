@@ -350,3 +350,29 @@ def test_wall_budget_drops_lowest_priority_records_and_keeps_the_reserve():
     assert rep["skipped_for_budget"] == ["second"] and rep["used_s"] == 113.0
     assert rep["seconds"] == {"first": 55.0, "third": 8.0, "never_dropped": 50.0}
     assert not b.take("late", 1.0) and b.left() == -13.0
+
+
+def test_dump_outputs_writes_the_last_sweep_as_float64_under_64_mb(tmp_path):
+    """--dump-outputs: every per-theta result and a fixed, seeded sample of the weights; two dumps of the same results are
+    identical, and the headline's 8 x 1e6 weights stay under 64 MB."""
+    def results(n, k):
+        rng = np.random.default_rng(3)
+        return [{"theta": 10.0 ** -i, "fmin": rng.normal(), "chi2": rng.normal(), "S": -rng.random(), "iterations": 7 + i,
+                 "evaluations": 9 + i, "code": 0, "seconds": rng.random(), "rank": 0, "w": rng.random(n)} for i in range(k)]
+    res = results(1000000, 8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res)
+    files = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert files == sorted(k + ".npy" for k in ("theta", "fmin", "chi2", "S", "iterations", "evaluations", "code", "w", "w_index"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64e6
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    idx = np.load(tmp_path / "a" / "w_index.npy").astype(np.int64)
+    w = np.load(tmp_path / "a" / "w.npy")
+    assert w.shape == (8, idx.size) and np.all(np.diff(idx) > 0)
+    assert all(np.array_equal(w[k], r["w"][idx]) for k, r in enumerate(res))
+    assert np.array_equal(np.load(tmp_path / "a" / "iterations.npy"), [r["iterations"] for r in res])
+    small = results(300, 3)                                  # small problems: every weight
+    bench.dump_outputs(str(tmp_path / "c"), small)
+    assert np.array_equal(np.load(tmp_path / "c" / "w.npy"), np.stack([r["w"] for r in small]))

@@ -1,8 +1,8 @@
 #!/bin/bash
-# Run ON THE GPU BOX (through gpurun): the default bench under rocprofv3 --kernel-trace --stats, the two PMC
+# Run ON THE GPU BOX: `bench.py --full` under rocprofv3 --kernel-trace --stats, the two PMC
 # passes the MI355X guide prescribes for HBM traffic (FETCH_SIZE and WRITE_SIZE cannot share a pass; the DEER
-# record is left out of them so that only the two headline sizes launch the strip kernels), then the default
-# bench unprofiled with those traffic figures in place.  usage: tools/profile_round.sh <tag>
+# record is left out of them so that only the two headline sizes launch the strip kernels), then `bench.py --full`
+# unprofiled with those traffic figures in place.  usage: tools/profile_round.sh <tag>
 set -e
 TAG=${1:-r05}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
@@ -12,19 +12,19 @@ mkdir -p $OUT
 # preloaded library has initialised the GPU by then, and an exec after that is forbidden on this pool)
 PY=$(readlink -f "$(command -v python3)")
 head -c 4 "$PY" | grep -q ELF || { echo "profile_round.sh: $PY is not an ELF binary" >&2; exit 2; }
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o $TAG -- $PY bench.py --no-cpu-baseline --no-api --no-one-copy > $OUT/stats.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o $TAG -- $PY bench.py --full --no-cpu-baseline --no-api --no-one-copy > $OUT/stats.log 2>&1
 echo "stats done"
-timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o $TAG -- $PY bench.py --no-cpu-baseline --no-api --no-deer --no-ala5 --no-storage-experiment --no-one-copy --warmup 0 > $OUT/fetch.log 2>&1
+timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o $TAG -- $PY bench.py --full --no-cpu-baseline --no-api --no-deer --no-ala5 --no-storage-experiment --no-one-copy --warmup 0 > $OUT/fetch.log 2>&1
 echo "fetch done"
-timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o $TAG -- $PY bench.py --no-cpu-baseline --no-api --no-deer --no-ala5 --no-storage-experiment --no-one-copy --warmup 0 > $OUT/write.log 2>&1
+timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o $TAG -- $PY bench.py --full --no-cpu-baseline --no-api --no-deer --no-ala5 --no-storage-experiment --no-one-copy --warmup 0 > $OUT/write.log 2>&1
 echo "write done"
 mkdir -p $OUT/profiles
 cp profiles/traffic.json $OUT/profiles/ 2>/dev/null || true
 PROFILES_OUT=$OUT/profiles python tools/summarize_profiles.py $TAG $OUT/stats $OUT/fetch $OUT/write --key 1000000 1024 --fkey 1000000 512 > $OUT/summary.log
 cp $OUT/stats/${TAG}_kernel_stats.csv $OUT/kernel_stats.csv
-# the default bench last, with the traffic figures of THESE sources in place (bench.py copies them into roofline.traffic)
+# the full bench last, with the traffic figures of THESE sources in place (bench.py copies them into roofline.traffic)
 cp $OUT/profiles/traffic.json profiles/traffic.json
-timeout -k 10 600 python bench.py > $OUT/bench_N1.json 2> $OUT/bench_N1.err
+timeout -k 10 600 python bench.py --full > $OUT/bench_N1.json 2> $OUT/bench_N1.err
 echo "bench done"
 # the launch-bound regime: wall time per lock-step round (both engines, one process, interleaved) and the per-kernel split
 REPS=4 SIZES=256:100000,1024:125000,205:500000,64:20000,28:50001 VARIANTS=device,host,host-nospec timeout -k 10 300 python tools/engine_ab.py > $OUT/engine_ab.txt 2>&1
