@@ -127,6 +127,13 @@ _SIGNATURES = {
     "bioen_hip_exchange_counts3": (C.c_int, [ctx_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                              C.POINTER(C.c_longlong)]),
     "bioen_hip_ctx_set_wait_timeout": (C.c_int, [ctx_p, C.c_double]),
+    "bioen_hip_bfgs_logw_begin": (C.c_int, [ctx_p, dp, dp, C.c_double, C.c_int, dp, dp, dp, dp]),
+    "bioen_hip_bfgs_logw_trial": (C.c_int, [ctx_p, C.c_double, C.c_int, dp, dp]),
+    "bioen_hip_bfgs_logw_accept": (C.c_int, [ctx_p, C.c_double, C.c_int, dp, dp, dp]),
+    "bioen_hip_bfgs_logw_update": (C.c_int, [ctx_p, dp, C.POINTER(C.c_int)]),
+    "bioen_hip_bfgs_logw_end": (C.c_int, [ctx_p, dp, dp, C.POINTER(OptResult)]),
+    "bioen_hip_bfgs_logw_read_hinv": (C.c_int, [ctx_p, C.c_int, C.c_int, C.c_int, dp]),
+    "bioen_hip_bfgs_logw_read_vec": (C.c_int, [ctx_p, C.c_int, dp]),
 }
 
 _lib = None
@@ -421,10 +428,11 @@ class Context(object):
         return out
 
     def footprint(self):
-        """(forms, bytes) of the resident copies of the matrix: forms is a set out of {"rowmajor", "strips", "strips_colsum"}"""
+        """(forms, bytes) of the resident copies of the matrix: forms is a set out of {"rowmajor", "strips", "strips_colsum"};
+        plus "bfgs_hinv" and its N x N bytes while a BFGS session (bfgs_logw) is live"""
         f, b = C.c_int(0), C.c_longlong(0)
         check(lib().bioen_hip_ctx_footprint(self._h, C.byref(f), C.byref(b)))
-        names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced"}
+        names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced", 16: "bfgs_hinv"}
         return {names[k] for k in names if f.value & k}, b.value
 
     def layout(self):
@@ -538,6 +546,81 @@ class Context(object):
                                                    C.byref(vis), int(max_batch), ptr(res),
                                                    ptr(w) if want_weights else None, infos))
         return res, w, list(infos)
+
+    # -- dense inverse-Hessian BFGS (scipy's fmin_bfgs on the device: bioen_amd/bfgs.py) --------------------------------
+    def bfgs_logw(self, g0, G, theta, gtol=1e-5, norm=np.inf, maxiter=None, c1=1e-4, c2=0.9, xrtol=0, disp=False):
+        """scipy.optimize.fmin_bfgs of the log-weights objective with H, the N x N inverse Hessian, in HBM: scipy's loop
+        and line searches on the host (bioen_amd.bfgs), every vector on the device.  Unsharded contexts only.
+        -> (gopt, w, info); info: fmin, iterations, func_calls, grad_calls, warnflag, message, chi2, kl"""
+        from . import bfgs
+        g0, G = self._nvec(g0, "g0"), self._nvec(G, "G")
+        backend = bfgs.DeviceBackend(self, g0, G, theta)
+        try:
+            res = bfgs.minimize(backend, self.n, gtol=gtol, norm=norm, maxiter=maxiter, c1=c1, c2=c2, xrtol=xrtol,
+                                disp=disp)
+        except BaseException:
+            self._bfgs_abandon()
+            raise
+        g, w, end = backend.finish()
+        res.chi2, res.kl = end.chi2, end.kl
+        return g, w, res
+
+    def _bfgs_abandon(self):
+        if self._h is not None and "bfgs_hinv" in self.footprint()[0]:
+            try:
+                self.bfgs_end()
+            except BioenHipError:
+                pass
+
+    def bfgs_begin(self, g0, G, theta, norm_inf=True):
+        """-> (f0, |g0| (max norm if norm_inf, else 2-norm), |g0|_2, g0.p0) -- bioen_hip_bfgs_logw_begin"""
+        g0, G = self._nvec(g0, "g0"), self._nvec(G, "G")
+        o = [C.c_double(0.0) for _ in range(4)]
+        check(lib().bioen_hip_bfgs_logw_begin(self._h, ptr(g0), ptr(G), float(theta), int(bool(norm_inf)),
+                                              *[C.byref(v) for v in o]))
+        return tuple(v.value for v in o)
+
+    def bfgs_trial(self, alpha, need_grad):
+        """-> (f(x + alpha p), g(alpha).p or None)"""
+        f, d = C.c_double(0.0), C.c_double(0.0)
+        check(lib().bioen_hip_bfgs_logw_trial(self._h, float(alpha), int(bool(need_grad)), C.byref(f), C.byref(d)))
+        return f.value, (d.value if need_grad else None)
+
+    def bfgs_accept(self, alpha, norm_inf=True):
+        """-> (|g|, |p|_2, |x|_2) at the accepted point"""
+        o = [C.c_double(0.0) for _ in range(3)]
+        check(lib().bioen_hip_bfgs_logw_accept(self._h, float(alpha), int(bool(norm_inf)), *[C.byref(v) for v in o]))
+        return tuple(v.value for v in o)
+
+    def bfgs_update(self):
+        """-> (g.p of the next direction, whether y.s == 0 made rho = 1000)"""
+        d, fb = C.c_double(0.0), C.c_int(0)
+        check(lib().bioen_hip_bfgs_logw_update(self._h, C.byref(d), C.byref(fb)))
+        return d.value, bool(fb.value)
+
+    def bfgs_end(self):
+        """-> (x, w, OptResult with fmin, chi2, kl at x); frees H"""
+        g, w = np.empty(self.n), np.empty(self.n)
+        info = OptResult()
+        check(lib().bioen_hip_bfgs_logw_end(self._h, ptr(g), ptr(w), C.byref(info)))
+        return g, w, info
+
+    def bfgs_read_hinv(self, row0=0, rows=None, padded=False):
+        """rows [row0, row0 + rows) of the session's current inverse Hessian (debug / tests); padded: the stored form,
+        ld = N rounded up to 16 columns, pad rows and columns included"""
+        height = (self.n + 15) // 16 * 16 if padded else self.n
+        rows = height - row0 if rows is None else int(rows)
+        out = np.empty((rows, height))
+        check(lib().bioen_hip_bfgs_logw_read_hinv(self._h, int(row0), rows, int(bool(padded)), ptr(out)))
+        return out
+
+    BFGS_VECTORS = {"x": 0, "g": 1, "p": 2, "s": 3, "y": 4, "u": 5}
+
+    def bfgs_read_vec(self, which):
+        """a session vector: 'x', 'g', 'p', 's' (newest step), 'y' (newest), 'u' (H y of the pending update)"""
+        out = np.empty(self.n)
+        check(lib().bioen_hip_bfgs_logw_read_vec(self._h, self.BFGS_VECTORS[which], ptr(out)))
+        return out
 
     # -- forces -------------------------------------------------------------------
     def forces_weights(self, forces, w0):

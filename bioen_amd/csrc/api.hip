@@ -44,6 +44,10 @@ static int fail(int code, const char* msg) {
     return code;
 }
 
+// dense inverse-Hessian BFGS session (api_bfgs.inl): freed by destroy; ended by any other evaluation / optimiser call
+static void bfgs_free(bioen_hip_ctx* c);
+static void bfgs_interrupt(bioen_hip_ctx* c);
+
 // ---------------------------------------------------------------------------------
 // allocation helpers
 // ---------------------------------------------------------------------------------
@@ -1020,6 +1024,7 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
         }
     }
     if (c->stream) hipStreamSynchronize(c->stream);
+    bfgs_free(c);
     bioen_hip_p2p_detach(c);
     bioen_hip_comm_destroy(c);
     resolve_timers(c);
@@ -1134,6 +1139,10 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
         if (c->Yr) { f |= 8; b += each; }
         if (c->Yr1) { f |= 8; b += each; }
     }
+    if (c->bfgs) {               // the live BFGS session's inverse Hessian (api_bfgs.inl)
+        f |= 16;
+        b += c->bfgs_hbytes;
+    }
     if (forms) *forms = f;
     if (bytes) *bytes = b;
     return 0;
@@ -1200,6 +1209,7 @@ int bioen_hip_synchronize(bioen_hip_ctx* c) {
 
 // ---- log-weights ----------------------------------------------------------------------
 int bioen_hip_logw_weights(bioen_hip_ctx* c, const double* g, double* w, double* log_s) {
+    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
     if (!c || !g) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     BIOEN_HIP_CHECK(hipSetDevice(c->device));
     ProblemSlot& s0 = c->slot[0];
@@ -1222,6 +1232,7 @@ int bioen_hip_logw_weights(bioen_hip_ctx* c, const double* g, double* w, double*
 
 int bioen_hip_logw_fdf(bioen_hip_ctx* c, const double* g, const double* G, double theta, double* f,
                        double* grad) {
+    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
     if (!c || !g || !G) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     BIOEN_HIP_CHECK(hipSetDevice(c->device));
     ProblemSlot& s0 = c->slot[0];
@@ -1297,6 +1308,7 @@ int bioen_hip_opt_lbfgs_logw_batch(bioen_hip_ctx* c, int ntheta, const double* t
                                    size_t g0_stride, const double* G, const bioen_lbfgs_config* config,
                                    const bioen_visual_params* visual, int max_batch, double* results,
                                    double* w_opt, bioen_opt_result* infos) {
+    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
     if (!c || !thetas || !g0 || !G || !config || !results || !infos || ntheta <= 0)
         return fail(BIOEN_HIP_EINVAL, "NULL argument or ntheta <= 0");
     if (g0_stride != 0 && g0_stride < (size_t)c->n_global)
@@ -1319,6 +1331,7 @@ int bioen_hip_opt_lbfgs_logw_batch(bioen_hip_ctx* c, int ntheta, const double* t
 int bioen_hip_opt_lbfgs_logw(bioen_hip_ctx* c, const double* g0, const double* G, double theta,
                              const bioen_lbfgs_config* config, const bioen_visual_params* visual,
                              double* result, double* w_opt, bioen_opt_result* info) {
+    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
     if (!info) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     return bioen_hip_opt_lbfgs_logw_batch(c, 1, &theta, g0, 0, G, config, visual, 1, result, w_opt, info);
 }
@@ -1342,6 +1355,7 @@ static int forces_guard(const bioen_hip_ctx* c, bool strip_path_ok = true) {
 }
 
 int bioen_hip_forces_weights(bioen_hip_ctx* c, const double* forces, const double* w0, double* w) {
+    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
     if (!c || !forces || !w0 || !w) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     int rc;
     if (forces_canonical(c) && !c->storage) {
@@ -1377,6 +1391,7 @@ int bioen_hip_forces_weights(bioen_hip_ctx* c, const double* forces, const doubl
 
 int bioen_hip_forces_fdf(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* f,
                          double* grad) {
+    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
     if (!c || !forces || !w0) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     int rc = forces_guard(c);
     if (rc) return rc;
@@ -1463,6 +1478,7 @@ int bioen_hip_debug_pass_probe(bioen_hip_ctx* c, int k, int reps, double* fwd_ms
 
 int bioen_hip_forces_fdf_batch(bioen_hip_ctx* c, int k, const double* forces, const double* w0, const double* thetas,
                                double* f, double* grad) {
+    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
     if (!c || !forces || !w0 || !thetas) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (k < 1 || k > kMaxBatch) return fail(BIOEN_HIP_EINVAL, "k must be in [1, 8]");
     int rc = forces_guard(c);
@@ -1494,6 +1510,7 @@ int bioen_hip_opt_lbfgs_forces_batch(bioen_hip_ctx* c, int ntheta, const double*
                                      size_t f0_stride, const double* w0, const bioen_lbfgs_config* config,
                                      const bioen_visual_params* visual, int max_batch, double* results,
                                      double* w_opt, bioen_opt_result* infos) {
+    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
     if (!c || !thetas || !forces0 || !w0 || !config || !results || !infos || ntheta <= 0)
         return fail(BIOEN_HIP_EINVAL, "NULL argument or ntheta <= 0");
     if (f0_stride != 0 && f0_stride < (size_t)c->m) return fail(BIOEN_HIP_EINVAL, "f0_stride must be 0 or >= m");
@@ -1516,6 +1533,7 @@ int bioen_hip_opt_lbfgs_forces_batch(bioen_hip_ctx* c, int ntheta, const double*
 int bioen_hip_opt_lbfgs_forces(bioen_hip_ctx* c, const double* forces0, const double* w0, double theta,
                                const bioen_lbfgs_config* config, const bioen_visual_params* visual,
                                double* result, double* w_opt, bioen_opt_result* info) {
+    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
     if (!info) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     // one problem; the batch width left over serves its line search's speculative trials (engine_forces.inl)
     return bioen_hip_opt_lbfgs_forces_batch(c, 1, &theta, forces0, 0, w0, config, visual, kMaxBatch, result, w_opt, info);
@@ -1523,6 +1541,7 @@ int bioen_hip_opt_lbfgs_forces(bioen_hip_ctx* c, const double* forces0, const do
 
 // ---- shared ---------------------------------------------------------------------------
 int bioen_hip_chi_squared(bioen_hip_ctx* c, const double* w, double* yave, double* chi2) {
+    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
     if (!c || !w) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     BIOEN_HIP_CHECK(hipSetDevice(c->device));
     ProblemSlot& s0 = c->slot[0];
@@ -2092,3 +2111,4 @@ int bioen_hip_comm_destroy(bioen_hip_ctx* c) {
 }  // extern "C"
 
 #include "api_multimin.inl"
+#include "api_bfgs.inl"

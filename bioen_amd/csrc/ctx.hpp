@@ -116,6 +116,8 @@ struct Xch {              // one stage, as the kernels see it
     int segcols;          // columns per segment
 };
 
+struct BfgsSession;   // dense inverse-Hessian BFGS session (api_bfgs.inl)
+
 struct KernelTimer {
     bool enabled = false;
     double total_ms[2] = {0.0, 0.0};
@@ -272,6 +274,12 @@ struct bioen_hip_ctx {
                                      // round's N-vector kernels nontemporal (kernels_logw.hip); set per run by the host-driven
     int nvec_nt_env = -1;            // engine from the batch's working set; BIOEN_HIP_NVEC_NT=0/1 forces it
     bioen::KernelTimer timer;
+
+    // dense inverse-Hessian BFGS session (api_bfgs.inl): H (ld^2 doubles) and its work vectors, live from
+    // bioen_hip_bfgs_logw_begin to _end; any other optimiser / evaluation call on the context ends it
+    bioen::BfgsSession* bfgs = nullptr;
+    long long bfgs_hbytes = 0;       // its H: ld^2 * 8 bytes (bioen_hip_ctx_footprint)
+    int bfgs_interrupted = 0;        // a session was ended by another call: the next bfgs call returns BIOEN_HIP_ESTATE
 
     // RCCL (lazy, dlopen)
     void* comm = nullptr;

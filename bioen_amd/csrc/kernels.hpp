@@ -173,6 +173,19 @@ void launch_vstep(bioen_hip_ctx* c, const double* x, const double* p, double coe
 void launch_vdots_part(bioen_hip_ctx* c, const VDotArgs& q);                                // block partials -> X_GRAD stage   [exchange]
 void launch_vdots_finish(bioen_hip_ctx* c, const VDotArgs& q, double* out);                 // out: device, k doubles
 
+// ---- dense inverse-Hessian BFGS (kernels_bfgs.hip; the session: api_bfgs.inl) --------------
+size_t bfgs_ld(int n);          // leading dimension of H: n rounded up to 16
+// one streaming pass: H <- H with the pending update (s, u, rho, cc) (first: H = I synthesised, not read), hy = H y, hg = H g
+void launch_bfgs_hpass(bioen_hip_ctx* c, double* H, size_t ld, bool first, const double* s, const double* u, double rho,
+                       double cc, const double* y, const double* g, double* hy, double* hg);
+// rows [row0, row0 + rows) of H with the pending update applied -> out (rows x ld, device)
+void launch_bfgs_hread(bioen_hip_ctx* c, const double* H, size_t ld, bool first, const double* s, const double* u,
+                       double rho, double cc, size_t row0, int rows, double* out);
+// p = -(((hg - a1 s) - a2 u) + a3 s); block partials of g.p, p.p -> X_GRAD stage (arrays 0, 1; launch_vdots_finish k = 2)
+void launch_bfgs_dir(bioen_hip_ctx* c, const double* hg, const double* s, const double* u, double a1, double a2,
+                     double a3, const double* g, double* p);
+void launch_bfgs_sub(bioen_hip_ctx* c, const double* a, const double* b, double* y);      // y = a - b (ld doubles)
+
 // ---- L-BFGS vector kernels (device-resident scalars) -------------------------------
 struct PairArgs {      // s = x - xp ; y = g - gp for the accepting problems
     int n;

@@ -151,6 +151,9 @@ def find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
     if str(cfg["minimizer"]).upper() not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY'):      # rejected before anything touches the device
         raise RuntimeError("Library " + cfg["minimizer"] +
                            " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy' ) ")
+    if str(cfg["minimizer"]).upper() == 'SCIPY' and cfg["params"].get("on_device"):
+        raise RuntimeError("scipy:on_device (scipy's BFGS with the inverse Hessian on the device) serves the "
+                           "log-weights method only (optimize.log_weights.find_optimum); the forces method has none")
     if not (str(cfg["minimizer"]).upper() == 'SCIPY' and not bool(cfg["use_c_functions"])):
         with c_bioen.hold(yTilde, YTilde):
             return _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg)

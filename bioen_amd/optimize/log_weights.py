@@ -210,6 +210,33 @@ def _uses_device(cfg):
     return not (str(cfg["minimizer"]).upper() == 'SCIPY' and not bool(cfg["use_c_functions"]))
 
 
+def _bfgs_on_device(cfg):
+    """scipy's BFGS with the inverse Hessian in HBM (bioen_amd.bfgs): opt-in through the scipy parameter `on_device`
+    (``Parameters("scipy", "scipy:on_device=true")``, or the CLI's ``--optimization_parameters scipy:on_device=true``).
+    Combinations it cannot serve raise instead of falling back."""
+    if str(cfg["minimizer"]).upper() != 'SCIPY' or not cfg["params"].get("on_device"):
+        return False
+    if str(cfg["algorithm"]).lower() not in ("bfgs", "fmin_bfgs"):
+        raise RuntimeError("scipy:on_device runs scipy's BFGS on the device; algorithm '" + str(cfg["algorithm"]) +
+                           "' has no device path (use 'bfgs' / 'fmin_bfgs', or drop on_device)")
+    if not bool(cfg["use_c_functions"]):
+        raise RuntimeError("scipy:on_device needs use_c_functions: true (the device objective); "
+                           "use_c_functions: false asks for the numpy objective on the host")
+    return True
+
+
+def _run_device_bfgs(cfg, gPrime, G, yTilde, YTilde, theta):
+    """fmin_bfgs's parameters (gtol, max_iterations, disp = verbose) on the device session; -> (gopt, fmin)"""
+    p = cfg["params"]
+    ctx, cached = c_bioen._context_for(yTilde, YTilde)
+    try:
+        gopt, _, info = ctx.bfgs_logw(np.asarray(gPrime, dtype=np.float64), np.asarray(G, dtype=np.float64).reshape(-1),
+                                      theta, gtol=p["gtol"], maxiter=p["max_iterations"], disp=bool(cfg["verbose"]))
+    finally:
+        c_bioen._release(ctx, cached)
+    return gopt, info.fmin
+
+
 def find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg):
     """Minimise the BioEn negative log-posterior over the n log-weights (log_weights.py:409-621): see `_find_optimum`.
     The matrix is HELD for the duration of the call (ext/c_bioen.py: hold): the initial objective, the optimisation and
@@ -220,6 +247,7 @@ def find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg):
     if str(cfg["minimizer"]).upper() not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY'):      # rejected before anything touches the device
         raise RuntimeError("Library " + cfg["minimizer"] +
                            " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy' ) ")
+    _bfgs_on_device(cfg)                                 # refused combinations raise here, before the device is touched
     if _uses_device(cfg):
         with c_bioen.hold(yTilde, YTilde):
             return _find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg)
@@ -264,6 +292,9 @@ def _find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg):
     elif minimizer == 'GSL':
         common.print_highlighted("LOGW -- Library GSL/C", cfg["verbose"])
         res = c_bioen.bioen_opt_bfgs_logw(gPrime, G, yTilde, YTilde, theta, cfg)
+    elif minimizer == 'SCIPY' and use_c and _bfgs_on_device(cfg):
+        common.print_highlighted("LOGW -- Library scipy-BFGS/HIP, inverse Hessian in HBM", cfg["verbose"])
+        res = _run_device_bfgs(cfg, gPrime, G, yTilde, YTilde, theta)
     elif minimizer == 'SCIPY' and use_c:
         common.print_highlighted("LOGW -- Library scipy/HIP", cfg["verbose"])
         dev = _DeviceFdf(G, yTilde, YTilde, theta)

@@ -321,6 +321,40 @@ int bioen_hip_debug_strip_stamps(bioen_hip_ctx* ctx, int enable, long long* out,
  * HIP events on the context's stream.  Produces and changes no result. */
 int bioen_hip_debug_pass_probe(bioen_hip_ctx* ctx, int k, int reps, double* fwd_ms, double* adj_ms);
 
+/* ---- dense inverse-Hessian BFGS session (log-weights): the vector backend of bioen_amd/bfgs.py -------------------
+ * scipy's fmin_bfgs (the reference's default minimizer) keeps H, the N x N inverse Hessian, as a host array and
+ * updates it with two dense N x N products per iteration.  Here H lives in HBM (ld x ld FP64, ld = N rounded up to
+ * 16) and is updated lazily in ONE streaming pass per iteration; the host driver keeps scipy's scalar decisions
+ * (its own line searches) and only scalars cross PCIe per trial.  UNSHARDED contexts only (world > 1: ESTATE).
+ *   begin   x = g0, objective and gradient at x, p = -g.  norm_inf: *gnorm = max |g| (else |g|_2); *gnorm2 = |g|_2;
+ *           *dphi0 = g.p.  Memory check first: when ld^2 * 8 bytes plus the work vectors exceed hipMemGetInfo's free
+ *           bytes it returns BIOEN_HIP_ENOMEM (message naming the N x N matrix) and allocates nothing.  A live session
+ *           on the context is ended first.
+ *   trial   *f = f(x + alpha p) (forward pass only); need_grad: also the adjoint at the same point, *dphi = g(alpha).p.
+ *           The same alpha again reuses what is in place.
+ *   accept  alpha must be the last trial, with its gradient: s = alpha p, x += s, y = g(alpha) - g, g = g(alpha);
+ *           -> the driver's norm of the new g, |p|_2, |x|_2 (scipy's stopping tests).
+ *   update  one pass over H (the previous step's rank-2 update + the row sums H [y, g]), the next direction
+ *           p = -H' g and *dphi0 = g.p; *rho_fallback = 1 when y.s == 0 (rho = 1000, as scipy).
+ *   end     optimum -> g_out, weights -> w_out (either may be NULL); info: fmin = f(x), chi2, kl, iterations = H passes.
+ *           Frees H.
+ * H is freed at _end, on every error of a bfgs call, and by bioen_hip_ctx_destroy; bioen_hip_ctx_footprint counts it
+ * (forms bit 16) while the session is live.  Any other evaluation or optimiser call on the context (logw_*, forces_*,
+ * opt_*, chi_squared) ends a live session: the session's next call returns BIOEN_HIP_ESTATE. */
+int bioen_hip_bfgs_logw_begin(bioen_hip_ctx* ctx, const double* g0, const double* G, double theta, int norm_inf,
+                              double* f0, double* gnorm, double* gnorm2, double* dphi0);
+int bioen_hip_bfgs_logw_trial(bioen_hip_ctx* ctx, double alpha, int need_grad, double* f, double* dphi);
+int bioen_hip_bfgs_logw_accept(bioen_hip_ctx* ctx, double alpha, int norm_inf, double* gnorm, double* pnorm,
+                               double* xnorm);
+int bioen_hip_bfgs_logw_update(bioen_hip_ctx* ctx, double* dphi0, int* rho_fallback);
+int bioen_hip_bfgs_logw_end(bioen_hip_ctx* ctx, double* g_out, double* w_out, bioen_opt_result* info);
+/* Debug / tests: rows [row0, row0 + rows) of the session's current H (the one whose product with g gave the current
+ * direction; scipy's Bopt at the end) -> out (rows x N); padded = 1: the stored form, rows < ld and ld columns, pads
+ * included (rows x ld); and a session vector -> out (N): which 0 = x, 1 = g, 2 = p,
+ * 3 = the newest step s, 4 = the newest y, 5 = u = H y of the pending update. */
+int bioen_hip_bfgs_logw_read_hinv(bioen_hip_ctx* ctx, int row0, int rows, int padded, double* out);
+int bioen_hip_bfgs_logw_read_vec(bioen_hip_ctx* ctx, int which, double* out);
+
 /* ---- host self-test of the L-BFGS driver (no GPU needed) ------------------------------
  * Runs the SAME driver + line-search code as the optimizers above on a built-in analytic
  * objective evaluated on the host: kind 0 = extended Rosenbrock, kind 1 = ill-conditioned
