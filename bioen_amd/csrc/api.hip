@@ -180,7 +180,7 @@ static int ctx_alloc(int m, long long n_global, int device, int rank, int world,
         const char* e = std::getenv("BIOEN_HIP_KEEP_ROWMAJOR");    // A/B: keep the row-major matrix beside the strip copies
         c->keep_rowmajor = (e && e[0] == '1') ? 1 : 0;
         e = std::getenv("BIOEN_HIP_ONE_COPY");         // log-weights on ONE strip copy (ctx.hpp: one_copy)
-        c->one_copy_wanted = (e && e[0] == '1') ? 1 : (e && e[0] == '0') ? 0 : -1;     // (-1: by size, kernels_strip.hip: one_copy_by_default)
+        c->one_copy_wanted = (e && e[0] == '1') ? 1 : (e && e[0] == '0') ? 0 : -1;     // (-1: by size, strip_plan.cpp: one_copy_by_default)
         e = std::getenv("BIOEN_HIP_FWD_STREAM");       // A/B: the streaming forward kernel on the row-major matrix
         c->fwd_stream = (e && e[0] == '1') ? 1 : 0;
         e = std::getenv("BIOEN_HIP_PANELS");           // A/B: M > 1024 on the r01 streaming kernels instead of row panels
@@ -605,9 +605,9 @@ static int enqueue_logw_eval(bioen_hip_ctx* c, const Round& r, bool with_grad) {
     }
     if (nblk > 0) {
         // matrix pass 1 streams the strip-major copy (M > 1024: row panel by row panel) straight into the matrix cores
-        // (kernels_strip.hip: k_strip_fwd) -- the same time for every batch width; the centre returns in
+        // (kernels_strip_logw.hip: k_strip_fwd) -- the same time for every batch width; the centre returns in
         // k_rows_combine, which leaves the RAW ybar in ybar_c for the centred adjoint below
-        launch_fwd_strip(c, r.n, w, nblk);
+        launch_fwd_strip(c, r.n, w);
         launch_fwd_rows_local(c, r.n, true, nblk, true);
         if ((rc = exchange(c, X_YBAR, (size_t)ybar_payload(c, r.n, true)))) return rc;
         launch_rows_combine(c, r, true, c->strip_center, true);
@@ -628,11 +628,11 @@ static int enqueue_logw_adjoint(bioen_hip_ctx* c, const Round& r) {
     MVec8 out{};
     for (int a = 0; a < r.n; ++a) out.p[a] = r.a[a];
     const int nblk = fwd_strip_blocks(c);
-    if (nblk > 0) {                              // matrix pass 2 on the column-sum strip copy (kernels_strip.hip)
+    if (nblk > 0) {                              // matrix pass 2 on the column-sum strip copy (kernels_strip_logw.hip)
         if ((rc = ensure_strip_copy_colsum(c))) return rc;
         MVec8 sc{};
         for (int a = 0; a < r.n; ++a) sc.p[a] = r.scal[a];
-        launch_adj_strip(c, r.n, c->r_c, out, sc, nblk);
+        launch_adj_strip(c, r.n, c->r_c, out, sc);
     } else {
         if ((rc = ensure_rowmajor(c))) return rc;
         launch_adj(c, r.n, c->r_c, out, true);   // A6: a_k = sum_i r_i (yTilde_ik - ybar_i)  [matrix pass 2]
@@ -689,14 +689,14 @@ static int enqueue_forces_eval(bioen_hip_ctx* c, const ForcesRound& fr, const Ro
         // Sharded contexts: every rank does this on its columns; the shares of ybar travel with the
         // rank's softmax totals in ONE all-gather (the layout of the log-weights rounds, finished by
         // the same k_rows_combine), the shares of the gradient in a second one.
-        // Both passes read the strip-major copy centred on the targets (kernels_strip.hip); ybar_c then holds
+        // Both passes read the strip-major copy centred on the targets (strip.hpp); ybar_c then holds
         // ybar - center, the row offset of k_rows_combine puts the centre back for r, chi^2 and f.
         launch_forces_xy(c, fr, nblk);        // F1 + F2: x, online softmax, this rank's ybar   [matrix pass 1]
         if ((rc = exchange(c, X_YBAR, (size_t)ybar_payload(c, fr.n, true)))) return rc;
         launch_rows_combine(c, r, true, c->strip_center, false);   //     normalisation, ybar (centred), r, chi^2, KL, f
         c->last_centered = true;               // ybar_c = ybar - strip_center (bioen_hip_last_average adds it back)
         if (with_grad) {
-            launch_forces_bt(c, fr, nblk);    // F3: b, t, product with t            [matrix pass 2]
+            launch_forces_bt(c, fr);          // F3: b, t, product with t            [matrix pass 2]
             launch_fwd_rows_forces_grad_share(c, fr.n, nblk, &fr, true);   // every segment's share (one GPU: all eight)
             if ((rc = exchange(c, X_YBAR, (size_t)c->mp * fr.n))) return rc;
             launch_forces_grad_sum_ranks(c, fr.n);                         // ... added in segment order
@@ -705,7 +705,7 @@ static int enqueue_forces_eval(bioen_hip_ctx* c, const ForcesRound& fr, const Ro
         }
         return 0;
     }
-    // M > 1024: four passes.  r03: on the strip kernels over row panels of <= 1024 rows (kernels_strip.hip) -- the two
+    // M > 1024: four passes.  r03: on the strip kernels over row panels of <= 1024 rows (strip.hpp) -- the two
     // column-sum passes uncentred, the two row-sum passes centred on the targets as in the two-pass path, T = sum_j t_j
     // taken off in the gradient's reduction -- with the r01 streaming kernels as the fallback (BIOEN_HIP_PANELS=0, or
     // no memory for the panel copies; unsharded contexts only).
@@ -729,20 +729,20 @@ static int enqueue_forces_eval(bioen_hip_ctx* c, const ForcesRound& fr, const Ro
             v.p[a] = fr.w[a];
         }
         const StripSets ss = strip_sets(c);
-        launch_adj_strip(c, fr.n, c->um, out, MVec8{}, psets, true);   // F1: x_j = sum_i f_i yTilde_ij   [matrix pass 1]
+        launch_adj_strip(c, fr.n, c->um, out, MVec8{}, true);          // F1: x_j = sum_i f_i yTilde_ij   [matrix pass 1]
         launch_max(c, rx);                                             //     block maxima of x per segment
         launch_forces_seg_exp(c, fr);                                  //     e = w0 exp(x - m_v) -> w ; shares of sum e, sum e x
-        launch_fwd_strip(c, fr.n, v, psets);                           // F2: (yTilde - centre) . e      [matrix pass 2]
+        launch_fwd_strip(c, fr.n, v);                                  // F2: (yTilde - centre) . e      [matrix pass 2]
         launch_fwd_rows_local(c, fr.n, true, psets, true);             //     the segments' shares + softmax totals
         if ((rc = exchange(c, X_YBAR, (size_t)ybar_payload(c, fr.n, true)))) return rc;
         launch_rows_combine(c, r, true, c->strip_center, false);       //     normalisation, ybar (centred), r, chi^2, KL, f
         c->last_centered = true;
         launch_scale_w(c, r);                                          //     w = e S_INV[v]: the weights
         if (with_grad) {
-            launch_adj_strip(c, fr.n, c->r_c, out, MVec8{}, psets, true);   // F3: b = yTilde^T r  [matrix pass 3]
+            launch_adj_strip(c, fr.n, c->r_c, out, MVec8{}, true);          // F3: b = yTilde^T r  [matrix pass 3]
             launch_forces_seg_t(c, fr, ss.gs * (ss.fold ? 1 : ss.nch));     //     t_j ; T_v = sum over segment v
             for (int a = 0; a < fr.n; ++a) v.p[a] = fr.t[a];
-            launch_fwd_strip(c, fr.n, v, psets);                            //     sum_j (yTilde_ij - c_i) t_j   [matrix pass 4]
+            launch_fwd_strip(c, fr.n, v);                                   //     sum_j (yTilde_ij - c_i) t_j   [matrix pass 4]
             launch_fwd_rows_forces_grad_share(c, fr.n, 0, &fr, false);      //     ... - (ybar_i - c_i) T_v, per segment
             if ((rc = exchange(c, X_YBAR, (size_t)c->mp * fr.n))) return rc;
             launch_forces_grad_sum_ranks(c, fr.n);                          //     added in segment order
@@ -1032,7 +1032,7 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
         hipEventDestroy(p.a);
         hipEventDestroy(p.b);
     }
-    double* bufs[] = {c->Y, c->Ys, c->Ys1, c->strip_center, c->zero_center, c->strip_stamps, c->YT, c->row_offset, c->row_scale, c->gram, c->ybar_c, c->r_c, c->um, c->gm, c->fixed,
+    double* bufs[] = {c->Y, c->strip_center, c->zero_center, c->strip_stamps, c->YT, c->row_offset, c->row_scale, c->gram, c->ybar_c, c->r_c, c->um, c->gm, c->fixed,
                       c->t, c->g0, c->fwd_partial, c->part, c->scal};
     for (double* p : bufs)
         if (p) hipFree(p);
@@ -1054,8 +1054,8 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
     if (c->live) hipHostFree(c->live);
     if (c->live2) hipHostFree(c->live2);
     for (int p = 0; p < bioen_hip_ctx::kMaxPanels; ++p) {
-        if (c->Yp[p]) hipFree(c->Yp[p]);
-        if (c->Y1p[p]) hipFree(c->Y1p[p]);
+        if (c->Ys[p]) hipFree(c->Ys[p]);
+        if (c->Ys1[p]) hipFree(c->Ys1[p]);
     }
     if (c->Yr) hipFree(c->Yr);
     if (c->Yr1) hipFree(c->Yr1);
@@ -1120,18 +1120,15 @@ int bioen_hip_ctx_layout(const bioen_hip_ctx* c, int* one_copy, int* interleave,
 int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes) {
     if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
     const long long rowmajor = (long long)c->mp * (long long)c->ld * 8;
-    const long long strips = (long long)(c->ld / 16) * ((c->m + 15) / 16 * 16) * 16 * 8;
     int f = 0;
     long long b = 0;
     if (c->Y) { f |= 1; b += rowmajor; }
-    if (c->Ys) { f |= 2; b += strips; }
-    if (c->Ys1) { f |= 4; b += strips; }
-    for (int p = 0; p < bioen_hip_ctx::kMaxPanels; ++p) {        // M > 1024: row panels of <= 1024 rows, both orders
+    for (int p = 0; p < bioen_hip_ctx::kMaxPanels; ++p) {        // the strip copies: row panels of <= 1024 rows, both orders
         const long long rows = std::min(1024, c->m - p * 1024);
         if (rows <= 0) break;
         const long long panel = (long long)(c->ld / 16) * ((rows + 15) / 16 * 16) * 16 * 8;
-        if (c->Yp[p]) { f |= 2; b += panel; }
-        if (c->Y1p[p]) { f |= 4; b += panel; }
+        if (c->Ys[p]) { f |= 2; b += panel; }
+        if (c->Ys1[p]) { f |= 4; b += panel; }
     }
     if (c->storage) {            // reduced-storage experiment: centred copies of 6 or 4 bytes per element, rows padded to 64 (128)
         const long long rows = (long long)round_up((size_t)c->m, c->mp > 512 ? 128 : 64);
@@ -1186,7 +1183,7 @@ int bioen_hip_ctx_set_storage(bioen_hip_ctx* c, int format) {
 
 int bioen_hip_ctx_set_one_copy(bioen_hip_ctx* c, int on) {
     if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
-    if (on && (c->Ys1 || c->Y1p[0])) return fail(BIOEN_HIP_ESTATE, "the column-sum order copy exists already: ask before the first gradient evaluation");
+    if (on && c->Ys1[0]) return fail(BIOEN_HIP_ESTATE, "the column-sum order copy exists already: ask before the first gradient evaluation");
     if (!on && c->one_copy) {        // back to two copies: the second one is built at the next gradient evaluation
         c->one_copy = 0;
     }
@@ -1455,13 +1452,13 @@ int bioen_hip_debug_pass_probe(bioen_hip_ctx* c, int k, int reps, double* fwd_ms
     float f_ms = 0.f, a_ms = 0.f;
     if (e == hipSuccess) {
         for (int i = 0; i < 2; ++i) {
-            launch_fwd_strip(c, k, w, nblk);
-            launch_adj_strip(c, k, c->r_c, out, sc, nblk);
+            launch_fwd_strip(c, k, w);
+            launch_adj_strip(c, k, c->r_c, out, sc);
         }
         e = hipEventRecord(ev[0], c->stream);
-        for (int i = 0; i < reps; ++i) launch_fwd_strip(c, k, w, nblk);
+        for (int i = 0; i < reps; ++i) launch_fwd_strip(c, k, w);
         if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
-        for (int i = 0; i < reps; ++i) launch_adj_strip(c, k, c->r_c, out, sc, nblk);
+        for (int i = 0; i < reps; ++i) launch_adj_strip(c, k, c->r_c, out, sc);
         if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
         if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
         if (e == hipSuccess) e = hipEventElapsedTime(&f_ms, ev[0], ev[1]);
@@ -1555,14 +1552,14 @@ int bioen_hip_chi_squared(bioen_hip_ctx* c, const double* w, double* yave, doubl
     Vec8 v{};
     v.p[0] = s0.w;
     int nblk = fwd_strip_blocks(c);
-    if (c->mp > 1024 && !c->Yp[0]) nblk = 0;      // row panels are built for the optimizer's passes, not for one product
+    if (c->mp > 1024 && !c->Ys[0]) nblk = 0;      // row panels are built for the optimizer's passes, not for one product
     if (c->storage) nblk = 0;                     // reduced-storage experiment: its copies are pre-centred; the FP64 matrix serves
     if (nblk > 0 && (rc = ensure_strip_copy(c))) {
         if (!c->strips_unavailable) return rc;
         nblk = 0;
     }
     if (nblk > 0) {            // the strip copy, uncentred (any w, not only normalised ones)
-        launch_fwd_strip(c, 1, v, nblk, true);
+        launch_fwd_strip(c, 1, v, true);
         launch_fwd_rows_local(c, 1, false, nblk, true);
     } else {
         if ((rc = ensure_rowmajor(c))) return rc;
@@ -1909,9 +1906,9 @@ int bioen_hip_read_probe(bioen_hip_ctx* c, int form, int reps, double* gbytes_pe
     if (!c || !gbytes_per_s || reps <= 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
     BIOEN_HIP_CHECK(hipSetDevice(c->device));
     // form: 0 = whichever is resident (strip copy first), 1 = row-major, 2 = row-sum strips, 4 = column-sum strips
-    // (matrices taller than 1024 rows keep their strip copies as row panels: the first panel stands for the form)
-    const double* ys = c->Ys ? c->Ys : c->Yp[0];
-    const double* ys1 = c->Ys1 ? c->Ys1 : c->Y1p[0];
+    // (the strip copies are kept as row panels of <= 1024 rows: the first panel stands for the form)
+    const double* ys = c->Ys[0];
+    const double* ys1 = c->Ys1[0];
     const double* src = form == 1 ? c->Y : form == 2 ? ys : form == 4 ? ys1 : (ys ? ys : c->Y);
     if (!src) return fail(BIOEN_HIP_ESTATE, "that form of the matrix is not resident");
     const size_t strip_rows_ = (size_t)(std::min(c->m, 1024) + 15) / 16 * 16;

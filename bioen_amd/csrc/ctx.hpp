@@ -192,36 +192,33 @@ struct bioen_hip_ctx {
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;   // results of finished problems leave on this one (engine_logw.inl: deliveries)
 
-    double* Y = nullptr;       // mp x ld, row-major: the form data arrive in; M <= 1024: freed once the strip copy Ys
-                               // exists (kernels_strip.hip: ensure_strip_copy), back on demand (ensure_rowmajor);
-                               // (M > 1024: the copies are row panels, Yp / Y1p)
+    double* Y = nullptr;       // mp x ld, row-major: the form data arrive in; freed once the strip copy Ys exists
+                               // (kernels_strip_copy.hip: ensure_strip_copy), back on demand (ensure_rowmajor)
     int keep_rowmajor = 0;     // BIOEN_HIP_KEEP_ROWMAJOR=1: never free it (A/B)
     int rowmajor_rebuilt = 0;  // it was freed and has been re-created since
     double* zero_center = nullptr;   // mp zeros: "no centring" for the strip kernels (bioen_hip_chi_squared)
-    // M <= 1024 (kernels_strip.hip): strip-major copies of the RAW matrix, built on first use; the kernels centre the
-    // operands on strip_center on the fly
-    double* Ys = nullptr;            // [ld / 16][strip rows][16], row-sum operand order (forces, log-weights forward)
-    double* Ys1 = nullptr;           // the same strips in column-sum operand order (log-weights adjoint)
+    // Strip-major copies of the RAW matrix (strip.hpp, kernels_strip_copy.hip), built on first use; the kernels centre the
+    // operands on strip_center on the fly.  One list of row PANELS of <= 1024 rows per operand order: M <= 1024 is the
+    // one-panel case; beyond (r03) the matrix passes of both methods run the same kernels panel by panel.
+    static constexpr int kMaxPanels = 16;
+    double* Ys[kMaxPanels] = {};     // panel p, rows [1024 p, 1024 (p + 1)): [ld / 16][strip rows][16], row-sum operand
+                                     // order (forces, log-weights forward)
+    double* Ys1[kMaxPanels] = {};    // the same strips in column-sum operand order (log-weights adjoint)
     double* strip_center = nullptr;  // mp: YTilde at the time of the copy
-    // reduced-byte storage EXPERIMENT (kernels_strip.hip; bioen_hip_ctx_set_storage): the log-weights passes stream
+    // reduced-byte storage EXPERIMENT (strip.hpp; bioen_hip_ctx_set_storage): the log-weights passes stream
     // CENTRED copies of 6 (fp32 + bf16 residual) or 4 (fp32) bytes per element; the row-major FP64 matrix stays resident
     int storage = 0;                 // 0 FP64 (default, the graded path) | 1 fp32 + bf16 split | 2 fp32
     void* Yr = nullptr;              // row-sum operand order
     void* Yr1 = nullptr;             // column-sum operand order
-    // M > 1024 (r03): the matrix passes of both methods run the same kernels over PANELS of <= 1024 rows, each with its
-    // own pair of strip copies; the row-major matrix is freed once the row-sum panels exist, as for M <= 1024
-    static constexpr int kMaxPanels = 16;
-    double* Yp[kMaxPanels] = {};     // row-sum order copy of rows [1024 p, 1024 (p + 1))
-    double* Y1p[kMaxPanels] = {};    // column-sum order copy
     int panel_off = 0;               // BIOEN_HIP_PANELS=0: the r01 streaming kernels for M > 1024 (A/B)
     double* strip_stamps = nullptr;  // diagnostic builds only: [block][16 waves][8] phase-cycle sums of the last strip launch
     int fwd_stream = 0;              // BIOEN_HIP_FWD_STREAM=1: log-weights forward pass by k_fwd_partial (A/B)
     int strips_unavailable = 0;      // a strip copy could not be allocated: the streaming kernels serve this context
     // r05: the log-weights method on ONE strip copy (the row-sum order one; the adjoint through the forces kernels' LDS image,
-    // kernels_strip.hip: k_strip<.., ADJ>): 1 x the matrix resident instead of 2 x.  wanted: BIOEN_HIP_ONE_COPY=1; taken
+    // kernels_strip512.hip: k_strip<.., ADJ>): 1 x the matrix resident instead of 2 x.  wanted: BIOEN_HIP_ONE_COPY=1; taken
     // by itself when the column-sum order copy cannot be allocated.  M <= 1024, FP64 storage.
     int one_copy = 0, one_copy_wanted = -1;      // wanted: 1 / 0 asked for / refused, -1 (r06 default): by the matrix's size -- ONE copy above 1 GiB
-    int strip_ilv = 0;               // r06: segments interleaved in the row-sum order FP64 copies (kernels_strip.hip: strip_phys); 0: none built yet
+    int strip_ilv = 0;               // r06: segments interleaved in the row-sum order FP64 copies (strip.hpp: strip_phys); 0: none built yet
     int strip_relayouts = 0;         // times the copies were moved to another method's layout
     int strip_allocs = 0;            // strip-copy allocations attempted on this context (tests: BIOEN_HIP_TEST_FAIL_STRIP_ALLOC=k fails the k-th)
     double* YT = nullptr;      // mp   experimental targets (YTilde)

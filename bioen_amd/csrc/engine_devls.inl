@@ -376,11 +376,11 @@ int LogwBatchEngine::run_device(int ntheta, const double* thetas, const double* 
             if (e) nblk = 0;
         }
         if (nblk > 0) {
-            launch_fwd_strip(c, k, wv, nblk);
+            launch_fwd_strip(c, k, wv);
             launch_fwd_rows_local(c, k, true, nblk, true);
             note(exchange(c, X_YBAR, (size_t)ybar_payload(c, k, true)));
             launch_rows_combine(c, rd, true, c->strip_center, true, &gate);
-            launch_adj_strip(c, k, c->r_c, av, sv, nblk);
+            launch_adj_strip(c, k, c->r_c, av, sv);
         } else {
             note(ensure_rowmajor(c));
             launch_fwd_partial(c, k, wv);

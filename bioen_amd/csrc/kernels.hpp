@@ -1,6 +1,8 @@
-// Host-side launch API of the gfx950 kernels (definitions: kernels_strip.hip -- the matrix passes for M <= 1024 and, over
-// row panels, beyond --, kernels_matrix.hip, kernels_logw.hip, kernels_forces.hip, kernels_devls.hip, kernels_misc.hip,
-// kernels_p2p.hip -- the peer-to-peer stage exchange; shared device helpers: device_utils.hpp).
+// Host-side launch API of the gfx950 kernels (definitions: strip_plan.cpp -- the matrix passes for M <= 1024 and, over
+// row panels, beyond: kernels in kernels_strip512.hip, kernels_strip1024.hip, kernels_strip_logw.hip, the copies they read
+// in kernels_strip_copy.hip, what those files share in strip.hpp --, kernels_matrix.hip, kernels_logw.hip,
+// kernels_forces.hip, kernels_devls.hip, kernels_misc.hip, kernels_p2p.hip -- the peer-to-peer stage exchange; shared
+// device helpers: device_utils.hpp).
 // Every function enqueues on ctx->stream and returns without synchronising.
 //
 // All kernels are batched: a launch serves the K (<= kMaxBatch) problems listed in a
@@ -64,7 +66,7 @@ void launch_fwd_rows_local(bioen_hip_ctx* c, int K, bool logw, int ctiles = 0, b
 int ybar_payload(const bioen_hip_ctx* c, int K, bool logw);        // doubles per rank in the X_YBAR stage
 void launch_scale_w(bioen_hip_ctx* c, const Round& r);              // w = e * scal[S_INV] (when a result is handed out)
 // add the ranks' shares -> ybar_c, r_c (compact), chi^2 / ybar.r partials per problem
-// center != NULL: the shares are sums over the CENTRED copy (kernels_strip.hip): ybar_raw = share + center;
+// center != NULL: the shares are sums over the CENTRED operand (strip.hpp): ybar_raw = share + center;
 // ybar_c keeps ybar_raw (store_raw: what k_adj's centring and the callers expect) or the centred share (the
 // forces strip pass 2, whose gradient correction is written in terms of it)
 struct DevGate {                      // device-resident engine: skip the problems the device has finished (kernels.hpp: DevSlot)
@@ -105,23 +107,23 @@ void launch_read_probe(bioen_hip_ctx* c, const double* p, size_t doubles, double
 void launch_forces_publish(bioen_hip_ctx* c, int ngrad, unsigned long long round);
 bool strip_panels(const bioen_hip_ctx* c);             // M > 1024: the strip kernels run over row panels
 int forces_fused_blocks(const bioen_hip_ctx* c);       // sets per segment of the forces strip passes; 0 when the context does not qualify
-void launch_forces_xy(bioen_hip_ctx* c, const struct ForcesRound& fr, int nblk);
-void launch_forces_bt(bioen_hip_ctx* c, const struct ForcesRound& fr, int nblk);
+void launch_forces_xy(bioen_hip_ctx* c, const struct ForcesRound& fr, int seg_sets);    // seg_sets: forces_fused_blocks, the merge's sets per segment
+void launch_forces_bt(bioen_hip_ctx* c, const struct ForcesRound& fr);
 void launch_forces_w_from_x(bioen_hip_ctx* c, const struct ForcesRound& fr);   // w = w0 exp(x - S_LOGS)
 // every local segment's share of the forces gradient -> its part of X_YBAR.  tposed: the two-pass strip kernels' sets (seg_sets per
 // segment); else the log-weights forward kernel's sets (row panels, M > 1024)
 void launch_fwd_rows_forces_grad_share(bioen_hip_ctx* c, int K, int seg_sets, const struct ForcesRound* tsum = nullptr, bool tposed = false);
 // builds ctx->Ys on first use; method 0 / 1: the log-weights / the forces passes come next and want the copy in their
-// layout (kernels_strip.hip: strip_phys; an existing copy is moved, best effort), -1: whatever is there
+// layout (strip.hpp: strip_phys; an existing copy is moved, best effort), -1: whatever is there
 int ensure_strip_copy(bioen_hip_ctx* c, int method = -1);
 int set_storage_format(bioen_hip_ctx* c, int fmt);     // reduced-byte storage experiment of the log-weights passes (0 = FP64)
 int fwd_strip_blocks(const bioen_hip_ctx* c);          // > 0: the log-weights forward pass runs on the strip copy
-void launch_fwd_strip(bioen_hip_ctx* c, int K, const Vec8& v, int nblk, bool plain = false);
+void launch_fwd_strip(bioen_hip_ctx* c, int K, const Vec8& v, bool plain = false);
 int ensure_rowmajor(bioen_hip_ctx* c);                 // the row-major matrix back from the strip copy (it is freed once that exists)
 int gather_block(bioen_hip_ctx* c, int row0, int rows, size_t col0, int cols, double* out);   // -> device out[rows][cols]
 int ensure_strip_copy_colsum(bioen_hip_ctx* c);        // builds ctx->Ys1 (column-sum operand order) on first use
-void launch_adj_strip(bioen_hip_ctx* c, int K, const double* u_c, const MVec8& out, const MVec8& scal, int nblk, bool plain = false);
-void launch_forces_blockmerge(bioen_hip_ctx* c, const struct ForcesRound& fr, int seg_sets, bool tposed = true);
+void launch_adj_strip(bioen_hip_ctx* c, int K, const double* u_c, const MVec8& out, const MVec8& scal, bool plain = false);
+void launch_forces_blockmerge(bioen_hip_ctx* c, const struct ForcesRound& fr, int seg_sets);    // pass 1's sets -> segment totals, ybar' shares
 void launch_forces_grad_sum_ranks(bioen_hip_ctx* c, int K);                     //          shares -> gm
 // adjoint: out_a[j] = sum_i (Y[i][j] - [centred] ybar_c[i*K+a]) u_c[i*K+a]
 void launch_adj(bioen_hip_ctx* c, int K, const double* u_c, const MVec8& out, bool centred = false);

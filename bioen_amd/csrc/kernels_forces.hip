@@ -1,7 +1,9 @@
-// Forces method: N-vector kernels of the four-pass paths (gfx950; M > 1024).  Two families: the r01 kernels of the
+// Forces method: the N-vector kernels (gfx950).  M > 1024, the four-pass paths, in two families: the r01 kernels of the
 // streaming fallback (no row panels: BIOEN_HIP_PANELS=0 or no memory for them; unsharded contexts only -- their partial
 // sums are plain per-block arrays), and the canonical-segment kernels of the row-panel path (r05, below), whose sums
-// are those of ctx.hpp's eight segments on any number of ranks.
+// are those of ctx.hpp's eight segments on any number of ranks.  M <= 1024: the merge of the sets the two strip passes
+// leave (k_strip / k_strip2: kernels_strip512.hip, kernels_strip1024.hip; launched from strip_plan.cpp) and the weights
+// from x.
 #include "device_utils.hpp"
 
 namespace bioen {
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_forces_scalars(ForcesRound r, int np
 
 // ---- canonical segments (r05): the four passes over row panels (M > 1024) on any number of ranks --------------------
 // The softmax over all structures is merged segment by segment exactly as in the two-pass strip path
-// (kernels_strip.hip: k_forces_blockstats) and in the log-weights rounds: e_j = w0_j exp(x_j - m_v) with the maximum
+// (k_forces_blockstats, below) and in the log-weights rounds: e_j = w0_j exp(x_j - m_v) with the maximum
 // m_v of the block's own SEGMENT, the block's shares of sum e and sum e x, and m_v go to the X_EXP stage in
 // k_logw_exp's layout, ride on the segment's part of X_YBAR behind the row sums of yTilde . e (k_fwd_rows_local_t) and
 // k_rows_combine<true> finishes: S_LOGS = M + log sum, S_P = sum_j w_j x_j, KL = S_P - S_LOGS, f.  One exchange.
@@ -194,6 +196,85 @@ void launch_forces_scalars(bioen_hip_ctx* c, const ForcesRound& r) {
     hipLaunchKernelGGL(k_forces_scalars, dim3(1, r.n), dim3(kBlock), 0, c->stream, r, combine_grid(c), vec_blocks(c));
 }
 
+
+// ---- the two-pass strip path (M <= 1024): merge of the sets of pass 1 ------------------------------------------------
+// Merge the sets of the xy pass per SEGMENT (one block per problem and local segment; set order): m_v = max_b m_b,
+// Z_v = sum_b e^{m_b - m_v} Z_b, likewise sum e x; P_MAX[b] <- e^{m_b - m_v}, the weight of set
+// b's raw sums.  The segment totals {Z_v, sum e x, m_v} go to the tail of the segment's part of X_YBAR --
+// the layout of the log-weights rounds -- so k_rows_combine<true> finishes both methods alike:
+//   scal[S_LOGS] = M + log Z  (w_j = w0_j exp(x_j - S_LOGS)),  scal[S_P] = sum_j w_j x_j,
+//   KL = sum_j w_j log(w_j / w0_j) = S_P - S_LOGS   (c_bioen_kernels_forces.c:246-258, with
+//   log w_j - log w0_j = x_j - S_LOGS; the prior constant S_LOGS0 is zero for this method).
+__global__ __launch_bounds__(kBlock) void k_forces_blockstats(ForcesRound fr, int seg_sets, int mp, int K, Xch xo) {
+    __shared__ double sh[kWaves];
+    const int a = blockIdx.y, v = blockIdx.z;
+    double* pa = fr.part[a];
+    double* pm = pa + (size_t)P_MAX * kPartStride + (size_t)v * seg_sets;
+    const double* ps = pa + (size_t)P_SUM * kPartStride + (size_t)v * seg_sets;
+    const double* pp = pa + (size_t)P_PP * kPartStride + (size_t)v * seg_sets;
+    const double mr = max_partials(pm, seg_sets, sh);
+    double z = 0.0, px = 0.0;
+    for (int b = threadIdx.x; b < seg_sets; b += kBlock) {
+        const double fb = exp(pm[b] - mr);
+        z = fma(fb, ps[b], z);
+        px = fma(fb, pp[b], px);
+    }
+    z = block_sum(z, sh);
+    px = block_sum(px, sh);
+    __syncthreads();
+    for (int b = threadIdx.x; b < seg_sets; b += kBlock) pm[b] = exp(pm[b] - mr);
+    if (threadIdx.x == 0) {
+        double* tail = xo.base + (size_t)(xo.rank + v) * xo.payload + (size_t)mp * K + 3 * a;
+        tail[0] = z;
+        tail[1] = px;
+        tail[2] = mr;
+        fr.scal[a][S_LOGS0] = 0.0;
+    }
+}
+
+// a segment's share of ybar' : sum_b weight_b raw_i,b over the segment's sets, on transposed partials (the strip kernels:
+// kernels_strip512.hip, kernels_strip1024.hip); blockIdx.y = local segment
+struct TermWeighted {
+    const double* wb;
+    __device__ __forceinline__ double operator()(int b, double v, double s) const { return fma(wb[b], v, s); }
+};
+
+__global__ __launch_bounds__(kBlock) void k_forces_rows_weighted_t(const double* __restrict__ partial, int seg_sets, int mp,
+                                                                   int K, ForcesRound fr, Xch xo) {
+    __shared__ double lds[8][32];
+    const int v = blockIdx.y;
+    const size_t n = (size_t)mp * K;
+    const size_t idx = (size_t)blockIdx.x * 32 + (threadIdx.x & 31);
+    const bool valid = idx < n;
+    const int a = (int)(idx % K);
+    const double* wb = fr.part[0];
+#pragma unroll
+    for (int k = 1; k < kMaxBatch; ++k)
+        if (k == a) wb = fr.part[k];
+    const double s = sets_sum8(partial + (size_t)v * seg_sets * n + (valid ? idx : 0), n, seg_sets, 1, lds,
+                               TermWeighted{wb + (size_t)P_MAX * kPartStride + (size_t)v * seg_sets});
+    if (threadIdx.x < 32 && valid) (xo.base + (size_t)(xo.rank + v) * xo.payload)[idx] = s;
+}
+
+// w_j = w0_j exp(x_j - S_LOGS): the weights themselves, when a result is handed out
+__global__ __launch_bounds__(kBlock) void k_forces_w_from_x(ForcesRound fr, const double* __restrict__ w0, int n) {
+    const int a = blockIdx.y;
+    const double* __restrict__ x = fr.a[a];
+    double* __restrict__ w = fr.w[a];
+    const double logz = fr.scal[a][S_LOGS];
+    for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) w[j] = w0[j] * exp(x[j] - logz);
+}
+
+void launch_forces_blockmerge(bioen_hip_ctx* c, const ForcesRound& fr, int seg_sets) {
+    const Xch xo = make_xch(c, X_YBAR, ybar_payload(c, fr.n, true));
+    hipLaunchKernelGGL(k_forces_blockstats, dim3(1, fr.n, c->vr), dim3(kBlock), 0, c->stream, fr, seg_sets, c->mp, fr.n, xo);
+    hipLaunchKernelGGL(k_forces_rows_weighted_t, dim3((c->mp * fr.n + 31) / 32, c->vr), dim3(kBlock), 0, c->stream,
+                       c->fwd_partial, seg_sets, c->mp, fr.n, fr, xo);
+}
+
+void launch_forces_w_from_x(bioen_hip_ctx* c, const ForcesRound& fr) {
+    hipLaunchKernelGGL(k_forces_w_from_x, dim3(vec_blocks(c), fr.n), dim3(kBlock), 0, c->stream, fr, c->fixed, c->n);
+}
 
 // ---- the round's results to the host without a copy engine and without a stream synchronisation (r03) -------------
 // page = [gradients, compact mp x k | scalars of all slots | flag]: one block copies both arrays into the host-mapped,

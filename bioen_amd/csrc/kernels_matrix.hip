@@ -396,7 +396,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_combine(Xch xi, int mp, int K, 
 
 // forces gradient (c_bioen_kernels_forces.c:330-338).  Streaming path: the partials already hold the centred
 // sums  sum_j (Y_ij - ybar_i) t_j ; only the column tiles remain to be added up.  Strip passes on the
-// centred copy (kernels_strip.hip): the partials hold sum_j Y'_ij t_j and  ybar'_i sum_j t_j  is taken off
+// centred operand (strip.hpp): the partials hold sum_j Y'_ij t_j and  ybar'_i sum_j t_j  is taken off
 // here, T = the blocks' shares of sum_j t_j in the problem's P_KL partials (every block re-sums them in the
 // same fixed order).
 __global__ __launch_bounds__(kBlock) void k_fwd_rows_forces_grad(const double* __restrict__ partial, int ctiles,
@@ -587,7 +587,7 @@ int ybar_payload(const bioen_hip_ctx* c, int K, bool logw) { return c->mp * K + 
 void launch_fwd_rows_local(bioen_hip_ctx* c, int K, bool logw, int ctiles, bool tposed) {
     const Xch xo = make_xch(c, X_YBAR, ybar_payload(c, K, logw));
     const Xch xe = make_xch(c, X_EXP, 3 * K * vec_grid(c));
-    if (tposed) {          // the strip kernels' sets (kernels_strip.hip: strip_sets)
+    if (tposed) {          // the strip kernels' sets (strip_plan.cpp: strip_sets)
         const StripSets ss = strip_sets(c);
         const int ntile = (c->mp * K + 31) / 32;
         if (logw)

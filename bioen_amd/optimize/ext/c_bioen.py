@@ -15,7 +15,7 @@ Differences from the reference, on purpose:
   ``find_optimum*`` hold the matrix for the duration of a call (ONE upload per call at any size), a caller
   looping over theta wraps its loop.
 * ``caching`` / ``cache_ytilde_transposed`` are accepted and ignored: both matrix passes stream
-  strip-major copies of the matrix built on the device (``csrc/kernels_strip.hip``); no host-side
+  strip-major copies of the matrix built on the device (``csrc/kernels_strip_copy.hip``, ``csrc/strip.hpp``); no host-side
   transposed copy exists.
 * ``bioen_log_posterior_logw`` uses its ``G`` argument.  The reference passes the
   *initial* log-weights ``g`` in the ``G`` slot (c_bioen.pyx:279), which is

@@ -820,7 +820,7 @@ def test_log_weights_on_one_strip_copy(M, N, monkeypatch):
 @pytest.mark.parametrize("M,N", [(37, 1000), (205, 20000), (512, 3000), (1024, 5000), (1100, 1500)])
 def test_strip_layout_follows_the_method_and_changes_no_bit(M, N, monkeypatch):
     """r06: the row-sum order strip copy holds the local segments' strips INTERLEAVED for the log-weights passes (one
-    contiguous window of the copy is read at any moment, kernels_strip.hip: strip_phys) and in strip order for the forces
+    contiguous window of the copy is read at any moment, csrc/strip.hpp: strip_phys) and in strip order for the forces
     passes; a context that changes method moves the copy.  Which layout served a call must not show in any bit: objective,
     gradient, capped batches of both methods, the matrix read back -- against a context that never interleaves
     (BIOEN_HIP_STRIP_INTERLEAVE=0, the r05 layout) and across the moves."""
