@@ -81,6 +81,7 @@ _SIGNATURES = {
     "bioen_hip_synchronize": (C.c_int, [ctx_p]),
     "bioen_hip_logw_weights": (C.c_int, [ctx_p, dp, dp, dp]),
     "bioen_hip_logw_fdf": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp]),
+    "bioen_hip_logw_hessp": (C.c_int, [ctx_p, dp, dp, C.c_double, C.c_int, dp, dp, dp, dp]),
     "bioen_hip_opt_lbfgs_logw": (C.c_int, [ctx_p, dp, dp, C.c_double, C.POINTER(LbfgsConfig),
                                            C.POINTER(VisualParams), dp, dp, C.POINTER(OptResult)]),
     "bioen_hip_opt_lbfgs_logw_batch": (C.c_int, [ctx_p, C.c_int, dp, dp, C.c_size_t, dp, C.POINTER(LbfgsConfig),
@@ -498,6 +499,38 @@ class Context(object):
                                        ptr(grad) if need_grad else None))
         return (f.value if need_f else None), grad
 
+    def logw_hessp(self, v, g=None, G=None, theta=None):
+        """Hessian-vector products H(g) v of the log-weights objective for up to 8 directions in one call: `v` is (n,) or
+        (k, n), the result has its shape.  With `g` (and G, theta) the point is evaluated first, as by logw_fdf, and kept on
+        the context: -> (hv, f, grad); `v` None then only sets the point: -> (None, f, grad).  Without `g` the product
+        refers to the point the last such call left: -> hv; BioenHipError (invalid state) once any other evaluation,
+        optimizer or change of the matrix state has run."""
+        if v is None:
+            if g is None or G is None or theta is None:
+                raise ValueError("logw_hessp without v sets the point: it needs g, G and theta")
+            g, G = self._nvec(g, "g"), self._nvec(G, "G")
+            f = C.c_double(0.0)
+            grad = np.empty(self.n)
+            check(lib().bioen_hip_logw_hessp(self._h, ptr(g), ptr(G), float(theta), 0, None, None, C.byref(f), ptr(grad)))
+            return None, f.value, grad
+        va = as_f64(v)
+        if va.ndim not in (1, 2) or va.shape[-1] != self.n:
+            raise ValueError("v must be (N,) or (k, N) with N = %d, got %s" % (self.n, (va.shape,)))
+        k = 1 if va.ndim == 1 else va.shape[0]
+        if k < 1 or k > 8:
+            raise ValueError("logw_hessp takes 1 to 8 directions per call, got %d" % k)
+        hv = np.empty_like(va)
+        if g is None:
+            check(lib().bioen_hip_logw_hessp(self._h, None, None, 0.0, k, ptr(va), ptr(hv), None, None))
+            return hv
+        if G is None or theta is None:
+            raise ValueError("logw_hessp with g needs G and theta")
+        g, G = self._nvec(g, "g"), self._nvec(G, "G")
+        f = C.c_double(0.0)
+        grad = np.empty(self.n)
+        check(lib().bioen_hip_logw_hessp(self._h, ptr(g), ptr(G), float(theta), k, ptr(va), ptr(hv), C.byref(f), ptr(grad)))
+        return hv, f.value, grad
+
     def opt_lbfgs_logw(self, g0, G, theta, params, verbose=False, debug=False, want_weights=True):
         g0, G = self._nvec(g0, "g0"), self._nvec(G, "G")
         cfg = lbfgs_config(params)
@@ -723,7 +756,8 @@ class Context(object):
 
     def kernel_stats(self):
         out = {}
-        for which, name in ((0, "forward"), (1, "adjoint")):
+        for which, name in ((0, "forward"), (1, "adjoint"), (2, "hessp_dots"), (3, "hessp_tangent"), (4, "hessp_combine"),
+                            (5, "hessp_epilogue")):
             ms = C.c_double(0.0)
             cnt = C.c_longlong(0)
             pp = C.c_longlong(0)

@@ -48,6 +48,16 @@ static int fail(int code, const char* msg) {
 static void bfgs_free(bioen_hip_ctx* c);
 static void bfgs_interrupt(bioen_hip_ctx* c);
 
+// Hessian-vector products (api_hessp.inl): the point a product refers to is dropped by everything that evaluates on the
+// context (bfgs_interrupt does it for the entries that call it) or changes the matrix state
+static void hessp_free(bioen_hip_ctx* c);
+static void point_drop(bioen_hip_ctx* c, const char* why) {
+    if (c && c->point_valid) {
+        c->point_valid = 0;
+        c->point_lost = why;
+    }
+}
+
 // ---------------------------------------------------------------------------------
 // allocation helpers
 // ---------------------------------------------------------------------------------
@@ -1025,6 +1035,7 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
     }
     if (c->stream) hipStreamSynchronize(c->stream);
     bfgs_free(c);
+    hessp_free(c);
     bioen_hip_p2p_detach(c);
     bioen_hip_comm_destroy(c);
     resolve_timers(c);
@@ -1146,6 +1157,7 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
 }
 
 int bioen_hip_ctx_set_ytilde_target(bioen_hip_ctx* c, const double* YTilde) {
+    point_drop(c, "the targets were changed (bioen_hip_ctx_set_ytilde_target)");
     if (!c || !YTilde) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     BIOEN_HIP_CHECK(hipSetDevice(c->device));
     BIOEN_HIP_CHECK(hipMemcpyAsync(c->YT, YTilde, (size_t)c->m * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1154,6 +1166,7 @@ int bioen_hip_ctx_set_ytilde_target(bioen_hip_ctx* c, const double* YTilde) {
 }
 
 int bioen_hip_ctx_set_affine(bioen_hip_ctx* c, const double* row_offset, const double* row_scale) {
+    point_drop(c, "the affine model was changed (bioen_hip_ctx_set_affine)");
     if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
     BIOEN_HIP_CHECK(hipSetDevice(c->device));
     std::vector<double> off(c->mp, 0.0), sc(c->mp, 1.0);
@@ -1173,6 +1186,7 @@ int bioen_hip_ctx_set_affine(bioen_hip_ctx* c, const double* row_offset, const d
 }
 
 int bioen_hip_ctx_set_storage(bioen_hip_ctx* c, int format) {
+    point_drop(c, "the storage format was changed (bioen_hip_ctx_set_storage)");
     if (!c || format < 0 || format > 2) return fail(BIOEN_HIP_EINVAL, "format must be 0 (FP64), 1 (fp32 + bf16 split) or 2 (fp32)");
     BIOEN_HIP_CHECK(hipSetDevice(c->device));
     if (format != 0 && c->mp > 1024) return fail(BIOEN_HIP_ESTATE, "the reduced-storage experiment serves M <= 1024");
@@ -1182,6 +1196,7 @@ int bioen_hip_ctx_set_storage(bioen_hip_ctx* c, int format) {
 }
 
 int bioen_hip_ctx_set_one_copy(bioen_hip_ctx* c, int on) {
+    point_drop(c, "the strip form was changed (bioen_hip_ctx_set_one_copy)");
     if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
     if (on && c->Ys1[0]) return fail(BIOEN_HIP_ESTATE, "the column-sum order copy exists already: ask before the first gradient evaluation");
     if (!on && c->one_copy) {        // back to two copies: the second one is built at the next gradient evaluation
@@ -1430,6 +1445,7 @@ int bioen_hip_debug_strip_stamps(bioen_hip_ctx* c, int enable, long long* out, i
 // Measurement aid (tools/pass_probe.py): the two log-weights matrix passes alone, `reps` launches each at batch width k on
 // whatever the slots' vectors hold, timed with events on the context's stream.  No result is produced or changed.
 int bioen_hip_debug_pass_probe(bioen_hip_ctx* c, int k, int reps, double* fwd_ms, double* adj_ms) {
+    point_drop(c, "the pass probe ran on the slots (bioen_hip_debug_pass_probe)");
     if (!c || !fwd_ms || !adj_ms || reps <= 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
     if (k < 1 || k > kMaxBatch) return fail(BIOEN_HIP_EINVAL, "k must be in [1, 8]");
     BIOEN_HIP_CHECK(hipSetDevice(c->device));
@@ -1619,7 +1635,7 @@ int bioen_hip_selftest_lbfgs(int kind, int n, const double* x0, const bioen_lbfg
 
 // ---- measurement ------------------------------------------------------------------------
 int bioen_hip_kernel_stats(bioen_hip_ctx* c, int which, double* total_ms, long long* launches) {
-    if (!c || which < 0 || which > 1) return fail(BIOEN_HIP_EINVAL, "bad argument");
+    if (!c || which < 0 || which >= kTimerKinds) return fail(BIOEN_HIP_EINVAL, "bad argument");
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     resolve_timers(c);
@@ -1641,9 +1657,11 @@ int bioen_hip_kernel_stats_reset(bioen_hip_ctx* c) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     resolve_timers(c);
-    c->timer.total_ms[0] = c->timer.total_ms[1] = 0.0;
-    c->timer.launches[0] = c->timer.launches[1] = 0;
-    c->timer.problem_passes[0] = c->timer.problem_passes[1] = 0;
+    for (int i = 0; i < kTimerKinds; ++i) {
+        c->timer.total_ms[i] = 0.0;
+        c->timer.launches[i] = 0;
+        c->timer.problem_passes[i] = 0;
+    }
     return 0;
 }
 
@@ -2109,3 +2127,4 @@ int bioen_hip_comm_destroy(bioen_hip_ctx* c) {
 
 #include "api_multimin.inl"
 #include "api_bfgs.inl"
+#include "api_hessp.inl"

@@ -48,6 +48,7 @@ static void bfgs_free(bioen_hip_ctx* c) {
 }
 
 static void bfgs_interrupt(bioen_hip_ctx* c) {
+    point_drop(c, "another evaluation or optimizer call ran on the context");
     if (c && c->bfgs) {
         bfgs_free(c);
         c->bfgs_interrupted = 1;
@@ -56,6 +57,7 @@ static void bfgs_interrupt(bioen_hip_ctx* c) {
 
 static int bfgs_session(bioen_hip_ctx* c, BfgsSession** S) {
     if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    point_drop(c, "a BFGS session ran on the context");
     if (!c->bfgs)
         return fail(BIOEN_HIP_ESTATE, c->bfgs_interrupted
                                           ? "the BFGS session was ended by another call on this context"
@@ -255,6 +257,7 @@ int bioen_hip_bfgs_logw_begin(bioen_hip_ctx* c, const double* g0, const double* 
     if (!c || !g0 || !G || !f0 || !gnorm || !gnorm2 || !dphi0) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (c->world > 1) return fail(BIOEN_HIP_ESTATE, "the BFGS session needs an unsharded context (world = 1)");
     BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    point_drop(c, "a BFGS session ran on the context");
     bfgs_free(c);
     c->bfgs_interrupted = 0;
     // memory check first: nothing is allocated for a matrix that cannot fit

@@ -118,11 +118,12 @@ struct Xch {              // one stage, as the kernels see it
 
 struct BfgsSession;   // dense inverse-Hessian BFGS session (api_bfgs.inl)
 
+constexpr int kTimerKinds = 6;     // 0 / 1: forward / adjoint matrix pass; 2..5: the Hessian-vector product's dots, tangent, combine, epilogue
 struct KernelTimer {
     bool enabled = false;
-    double total_ms[2] = {0.0, 0.0};
-    long long launches[2] = {0, 0};
-    long long problem_passes[2] = {0, 0};   // sum over launches of the batch width K
+    double total_ms[kTimerKinds] = {};
+    long long launches[kTimerKinds] = {};
+    long long problem_passes[kTimerKinds] = {};   // sum over launches of the batch width K
     struct Pair { hipEvent_t a, b; int which; int k; };
     std::vector<Pair> pending;
     std::vector<Pair> pool;
@@ -277,6 +278,19 @@ struct bioen_hip_ctx {
     bioen::BfgsSession* bfgs = nullptr;
     long long bfgs_hbytes = 0;       // its H: ld^2 * 8 bytes (bioen_hip_ctx_footprint)
     int bfgs_interrupted = 0;        // a session was ended by another call: the next bfgs call returns BIOEN_HIP_ESTATE
+
+    // Hessian-vector products (api_hessp.inl): "the point" kept by the last bioen_hip_logw_hessp call with g != NULL -- slot 0
+    // holds its e, gradient and scalars, c->fixed its G -- plus what the product needs beyond a slot: the raw averages, every
+    // segment's softmax factor (S_INV covers the local segments only) and the directions' work vectors.  Dropped by every
+    // call that evaluates anything or changes the matrix state (point_drop).
+    int point_valid = 0;
+    const char* point_lost = nullptr;    // what dropped it (for the message)
+    double point_theta = 0.0;
+    double* point_ybar = nullptr;        // mp: raw ybar of the point
+    double* point_fac = nullptr;         // nseg: e^{m_v - M} / S of the point
+    double* hp_scal = nullptr;           // kMaxBatch x kScalStride: the directions' scalars (S_B0, S_UY, vbar, v.grad)
+    double* hp_vec[2 * bioen::kMaxBatch] = {};   // per direction: v | t, then the centred adjoint c, then H v (ld doubles each,
+                                                 // allocated at a direction's first use, kept until the context is destroyed)
 
     // RCCL (lazy, dlopen)
     void* comm = nullptr;

@@ -1,7 +1,7 @@
 // Host-side launch API of the gfx950 kernels (definitions: strip_plan.cpp -- the matrix passes for M <= 1024 and, over
 // row panels, beyond: kernels in kernels_strip512.hip, kernels_strip1024.hip, kernels_strip_logw.hip, the copies they read
 // in kernels_strip_copy.hip, what those files share in strip.hpp --, kernels_matrix.hip, kernels_logw.hip,
-// kernels_forces.hip, kernels_devls.hip, kernels_misc.hip, kernels_p2p.hip -- the peer-to-peer stage exchange; shared
+// kernels_forces.hip, kernels_hessp.hip, kernels_devls.hip, kernels_misc.hip, kernels_p2p.hip -- the peer-to-peer stage exchange; shared
 // device helpers: device_utils.hpp).
 // Every function enqueues on ctx->stream and returns without synchronising.
 //
@@ -138,6 +138,27 @@ void launch_logw_logs0_merge(bioen_hip_ctx* c, const Round& r);   // scal[S_LOGS
 void launch_logw_grad(bioen_hip_ctx* c, const Round& r);    // gradient epilogue + g.d, g.g, x.x
 void launch_finish_eval(bioen_hip_ctx* c, const Round& r);  // scal[S_DG], S_GG, S_XX
 void launch_store_dginit(bioen_hip_ctx* c, int k, const MVec8& scal);   // scal[S_DGINIT] <- X_DGI
+
+// ---- Hessian-vector products of the log-weights objective (kernels_hessp.hip; blockIdx.y = direction a) -------------
+//   dw = w (v - vbar), dr = yTilde dw, c = centred adjoint of dr, (Hv)_k = (v_k - vbar) grad_k + w_k [theta (v_k - vbar) + c_k - v.grad]
+struct HesspArgs {
+    int n;                          // K directions
+    const double* v[kMaxBatch];
+    double* t[kMaxBatch];           // ONE work vector per direction: e (v - vbar) for the forward pass (the 1 / sum e stays
+                                    // with the M sums), overwritten by the adjoint pass with c, by the epilogue with H v
+    double* scal[kMaxBatch];        // the direction's scalars: S_B0, S_UY (adjoint pass), S_SPARE0 = vbar, S_SPARE1 = v . grad
+    const double* e;                // the point: exp(x - m_v), its gradient, its scalar slot (S_INV), every segment's factor,
+    const double* grad;             //   its raw averages
+    const double* pscal;
+    const double* fac;
+    const double* ybar;
+    double theta;
+};
+void launch_hessp_keep(bioen_hip_ctx* c, double* fac, double* ybar);   // after a K = 1 evaluation: factors from the X_YBAR tails, ybar_c -> ybar
+void launch_hessp_dots(bioen_hip_ctx* c, const HesspArgs& h);          // block partials of e.v, grad.v -> X_GRAD   [exchange]
+void launch_hessp_tangent(bioen_hip_ctx* c, const HesspArgs& h);       // finishes the sums; t = e (v - vbar)
+void launch_hessp_combine(bioen_hip_ctx* c, const HesspArgs& h, const double* center);   // shares -> r_c, ybar_c, S_B0, S_UY
+void launch_hessp_epilogue(bioen_hip_ctx* c, const HesspArgs& h);
 
 // ---- forces N-vector kernels (blockIdx.y = batch position) ---------------------------------
 struct ForcesRound {

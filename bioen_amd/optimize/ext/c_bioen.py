@@ -266,6 +266,16 @@ def grad_bioen_log_posterior_logw(gPrime, g, G, yTilde, YTilde, theta, caching=F
     return grad
 
 
+def hessp_bioen_log_posterior_logw(gPrime, p, g, G, yTilde, YTilde, theta, caching=False):
+    """H(gPrime) p of the log-weights objective on the device (Context.logw_hessp: the point is set by this call)"""
+    ctx, cached = _context_for(yTilde, YTilde)
+    try:
+        hv, _, _ = ctx.logw_hessp(np.asarray(p, dtype=np.float64).reshape(-1), g=gPrime, G=G, theta=theta)
+    finally:
+        _release(ctx, cached)
+    return hv
+
+
 def _gsl_finish(func, info):
     """c_bioen.pyx:432-438: {0, GSL_CONTINUE, GSL_ENOPROG} count as success"""
     if info.lbfgs_code in gsl_success:

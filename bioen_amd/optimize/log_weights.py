@@ -107,6 +107,14 @@ def grad_bioen_log_posterior(gPrime, g, G, yTilde, YTilde, theta, use_c=True, ca
     return grad_bioen_log_posterior_base(gPrime, g, G, yTilde, YTilde, theta)
 
 
+def hessp_bioen_log_posterior(gPrime, p, g, G, yTilde, YTilde, theta, use_c=True, caching=False):
+    """Hessian-vector product H(gPrime) p w.r.t. the n log-weights (no reference counterpart; the twin of
+    grad_bioen_log_posterior). use_c=True -> HIP kernels."""
+    if use_c:
+        return c_bioen.hessp_bioen_log_posterior_logw(gPrime, p, g, G, yTilde, YTilde, theta, caching=caching)
+    return hessp_bioen_log_posterior_base(gPrime, p, g, G, yTilde, YTilde, theta)
+
+
 def bioen_log_posterior_base(gPrime, g, G, yTilde, YTilde, theta):
     """Pure-numpy objective (log_weights.py:289-328).  Like the reference it writes the
     current point into `g` in place."""
@@ -135,24 +143,54 @@ def grad_bioen_log_posterior_base(gPrime, g, G, yTilde, YTilde, theta):
     return grad[:, 0]
 
 
+def hessp_bioen_log_posterior_base(gPrime, p, g, G, yTilde, YTilde, theta):
+    """Pure-numpy Hessian-vector product H(gPrime) p in closed form (exact, not Gauss-Newton; H is indefinite away from
+    the optimum).  With w = softmax(g), pbar = w . p and grad the gradient above:
+
+      dw   = w (p - pbar)
+      c    = yTilde^T dr - ybar . dr,   dr = yTilde dw
+      H p  = (p - pbar) grad + w [ theta (p - pbar) + c - p . grad ]
+    """
+    gp = _col(gPrime)
+    Gc = _col(G)
+    pc = _col(p)
+    w, _ = getWeights(gp)
+    yT = np.asarray(yTilde, dtype=np.float64)
+    ybar = yT.dot(w)
+    r = ybar - _col(YTilde)
+    dev = gp - Gc
+    grad = theta * w * (dev - w.T.dot(dev).item()) + w * (yT.T.dot(r) - ybar.T.dot(r).item())
+    dp = pc - w.T.dot(pc).item()
+    dr = yT.dot(w * dp)
+    c = yT.T.dot(dr) - ybar.T.dot(dr).item()
+    hp = dp * grad + w * (theta * dp + c - grad.T.dot(pc).item())
+    return hp[:, 0]
+
+
 # ------------------------------------------------------------------ optimizer
 class _DeviceFdf(object):
     """scipy asks for f(x) and f'(x) in separate calls at the same x; one fused device
     evaluation (two matrix passes) serves both."""
 
-    def __init__(self, G, yTilde, YTilde, theta):
+    def __init__(self, G, yTilde, YTilde, theta, keep_point=False):
         self.ctx, self._cached = c_bioen._context_for(yTilde, YTilde)
+        self._keep_point = keep_point       # the Newton drivers: every evaluation leaves the point for the products at it
         self.G = np.asarray(G, dtype=np.float64).reshape(-1)
         self.theta = theta
         self._x = None
         self._f = None
         self._g = None
+        self._point = False       # the context keeps self._x as the point of logw_hessp
 
     def _eval(self, x):
         x = np.asarray(x, dtype=np.float64).reshape(-1)
         if self._x is None or not np.array_equal(x, self._x):
-            self._f, self._g = self.ctx.logw_fdf(x, self.G, self.theta)
+            if self._keep_point:      # the same evaluation, same bits, and the point stays for hessp at this x
+                _, self._f, self._g = self.ctx.logw_hessp(None, g=x, G=self.G, theta=self.theta)
+            else:
+                self._f, self._g = self.ctx.logw_fdf(x, self.G, self.theta)
             self._x = x.copy()
+            self._point = self._keep_point
 
     def f(self, x, *unused):
         self._eval(x)
@@ -161,6 +199,18 @@ class _DeviceFdf(object):
     def fprime(self, x, *unused):
         self._eval(x)
         return self._g
+
+    def hessp(self, x, p, *unused):
+        """H(x) p: at an x not seen yet ONE device call sets the point and serves f, f' and the product; at the cached x
+        the product refers to the point the context keeps (two matrix passes, like a gradient)"""
+        x = np.asarray(x, dtype=np.float64).reshape(-1)
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if self._x is not None and self._point and np.array_equal(x, self._x):
+            return self.ctx.logw_hessp(p)
+        hv, self._f, self._g = self.ctx.logw_hessp(p, g=x, G=self.G, theta=self.theta)
+        self._x = x.copy()
+        self._point = True
+        return hv
 
     def close(self):
         c_bioen._release(self.ctx, self._cached)
@@ -177,9 +227,34 @@ _SCIPY_ALGORITHMS = {
 }
 
 
-def _run_scipy(cfg, f, fprime, x0, args, flavour, show_caching):
-    """The three scipy drivers of log_weights.py:464-598 / forces.py:389-518 as one table."""
+# Second-order drivers: they need Hessian-vector products, which only the log-weights method has (`hessp` of _run_scipy)
+_SCIPY_NEWTON = {
+    "newton_cg": "Newton-CG", "fmin_ncg": "Newton-CG",
+    "trust_ncg": "trust-region Newton-CG", "trust-ncg": "trust-region Newton-CG",
+}
+
+
+def _run_scipy_newton(cfg, f, fprime, hessp, x0, args):
+    """scipy's Newton-CG (line search) and trust-region Newton-CG on f, f' and H p; -> (xopt, fopt)"""
     key = cfg["algorithm"].lower()
+    p = cfg["params"]
+    verbose = cfg["verbose"]
+    common.print_highlighted('method ' + _SCIPY_NEWTON[key], verbose)
+    if key in ("newton_cg", "fmin_ncg"):
+        res = sopt.fmin_ncg(f, x0, fprime, fhess_p=hessp, args=args, avextol=p.get("xtol", 1e-5),
+                            maxiter=p["max_iterations"], full_output=True, disp=bool(verbose))
+        return res[0], res[1]
+    res = sopt.minimize(f, x0, args=args, method="trust-ncg", jac=fprime, hessp=hessp,
+                        options={"gtol": p["gtol"], "maxiter": p["max_iterations"], "disp": bool(verbose)})
+    return res.x, res.fun
+
+
+def _run_scipy(cfg, f, fprime, x0, args, flavour, show_caching, hessp=None):
+    """The three scipy drivers of log_weights.py:464-598 / forces.py:389-518 as one table; with `hessp` (the log-weights
+    method) also the Newton drivers of _SCIPY_NEWTON."""
+    key = cfg["algorithm"].lower()
+    if hessp is not None and key in _SCIPY_NEWTON:
+        return _run_scipy_newton(cfg, f, fprime, hessp, x0, args)
     if key not in _SCIPY_ALGORITHMS:
         raise RuntimeError("Method '" + cfg["algorithm"] + "' not recognized for scipy/" + flavour +
                            " library (valid values =  'lbfgs', 'bfgs', 'cg' ) ")
@@ -297,15 +372,15 @@ def _find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg):
         res = _run_device_bfgs(cfg, gPrime, G, yTilde, YTilde, theta)
     elif minimizer == 'SCIPY' and use_c:
         common.print_highlighted("LOGW -- Library scipy/HIP", cfg["verbose"])
-        dev = _DeviceFdf(G, yTilde, YTilde, theta)
+        dev = _DeviceFdf(G, yTilde, YTilde, theta, keep_point=str(cfg["algorithm"]).lower() in _SCIPY_NEWTON)
         try:
-            res = _run_scipy(cfg, dev.f, dev.fprime, gPrime, (), "c", True)
+            res = _run_scipy(cfg, dev.f, dev.fprime, gPrime, (), "c", True, hessp=dev.hessp)
         finally:
             dev.close()
     else:
         common.print_highlighted("LOGW -- Library scipy/PY", cfg["verbose"])
         res = _run_scipy(cfg, bioen_log_posterior_base, grad_bioen_log_posterior_base, gPrime,
-                         (g, G, yTilde, YTilde, theta), "py", False)
+                         (g, G, yTilde, YTilde, theta), "py", False, hessp=hessp_bioen_log_posterior_base)
     end = time.time()
     if cfg["verbose"]:
         print('time elapsed ', (end - start))

@@ -225,6 +225,11 @@ int bioen_hip_logw_weights(bioen_hip_ctx* ctx, const double* g, double* w, doubl
  * `f` and/or `grad` may be NULL (f-only skips the adjoint pass). */
 int bioen_hip_logw_fdf(bioen_hip_ctx* ctx, const double* g, const double* G, double theta,
                        double* f, double* grad);
+/* H(g) v for k <= 8 directions (v, hv: k x n, row-major).  g != NULL: evaluates the point first (as
+   bioen_hip_logw_fdf with a gradient; f, grad optional outputs) and keeps it; g == NULL: the point kept by the
+   last such call (G, theta ignored), BIOEN_HIP_ESTATE when it is gone.  k == 0 with g != NULL only sets the point. */
+int bioen_hip_logw_hessp(bioen_hip_ctx* ctx, const double* g, const double* G, double theta, int k,
+                         const double* v, double* hv, double* f, double* grad);
 /* _opt_lbfgs_logw, c_bioen_kernels_logw.c:581-669, with the liblbfgs loop
  * (lbfgs.c:245-641) device-resident.  result[n] = optimal log-weights;
  * w_opt[n] (optional, may be NULL) = softmax(result).
@@ -298,7 +303,8 @@ int bioen_hip_last_average(bioen_hip_ctx* ctx, double* yraw, double* yeff);
 
 /* ---- measurement hooks (bench.py) -------------------------------------------- */
 /* Average device time (HIP events on the context's stream) and launch count of the
- * two matrix-streaming kernels since the last reset. which: 0 = forward, 1 = adjoint. */
+ * two matrix-streaming kernels since the last reset. which: 0 = forward, 1 = adjoint; 2 .. 5 = the four kernels
+ * of bioen_hip_logw_hessp (dots, tangent, combine, epilogue). */
 int bioen_hip_kernel_stats(bioen_hip_ctx* ctx, int which, double* total_ms, long long* launches);
 /* as above, plus the sum over launches of the batch width (problems served per matrix pass) */
 int bioen_hip_kernel_stats_ex(bioen_hip_ctx* ctx, int which, double* total_ms, long long* launches,
