@@ -44,18 +44,49 @@ static int fail(int code, const char* msg) {
     return code;
 }
 
-// dense inverse-Hessian BFGS session (api_bfgs.inl): freed by destroy; ended by any other evaluation / optimiser call
-static void bfgs_free(bioen_hip_ctx* c);
-static void bfgs_interrupt(bioen_hip_ctx* c);
+static void bfgs_free(bioen_hip_ctx* c);      // dense inverse-Hessian BFGS session (api_bfgs.inl)
+static void hessp_free(bioen_hip_ctx* c);     // the buffers of the Hessian-vector products (api_hessp.inl)
 
-// Hessian-vector products (api_hessp.inl): the point a product refers to is dropped by everything that evaluates on the
-// context (bfgs_interrupt does it for the entries that call it) or changes the matrix state
-static void hessp_free(bioen_hip_ctx* c);
-static void point_drop(bioen_hip_ctx* c, const char* why) {
-    if (c && c->point_valid) {
+// The point a Hessian-vector product refers to (api_hessp.inl) is gone; `by`: an entry's name, or what failed
+static void point_drop(bioen_hip_ctx* c, const char* by) {
+    if (c->point_valid) {
         c->point_valid = 0;
-        c->point_lost = why;
+        c->point_lost = by;
     }
+}
+
+// The entry guard: the first statement of every extern "C" function that takes a context (bioen_hip_ctx_destroy, which
+// accepts NULL, has none) says there what the call does to the state other calls rely on (DESIGN 6c has the table):
+//   FX_DEVICE         it works on the device: the context's device becomes the thread's current one
+//   FX_DROPS_POINT    it evaluates on the context or changes the matrix state: the products' point is gone
+//   FX_ENDS_SESSION   it evaluates or optimises: a live BFGS session ends, and its next call returns BIOEN_HIP_ESTATE
+//   FX_NEEDS_SESSION  it is a call of the BFGS session: BIOEN_HIP_ESTATE without one
+// A NULL context is BIOEN_HIP_EINVAL.  The effects come before the entry looks at its other arguments: a call rejected
+// for those has had them all the same.
+enum : unsigned {
+    FX_NONE = 0,             // queries and settings: host fields only (the entries that take a const context pass this)
+    FX_DEVICE = 1,
+    FX_DROPS_POINT = 2,
+    FX_ENDS_SESSION = 4,
+    FX_NEEDS_SESSION = 8,
+    FX_CHANGES_MATRIX = FX_DEVICE | FX_DROPS_POINT,
+    FX_EVALUATES = FX_DEVICE | FX_DROPS_POINT | FX_ENDS_SESSION,
+    FX_SESSION_CALL = FX_DEVICE | FX_DROPS_POINT | FX_NEEDS_SESSION,
+};
+
+static int enter(const bioen_hip_ctx* ctx, unsigned fx, const char* who) {
+    if (!ctx) return fail(BIOEN_HIP_EINVAL, (std::string(who) + ": ctx is NULL").c_str());
+    bioen_hip_ctx* c = const_cast<bioen_hip_ctx*>(ctx);
+    if (fx & FX_DROPS_POINT) point_drop(c, who);
+    if ((fx & FX_ENDS_SESSION) && c->bfgs) {
+        bfgs_free(c);
+        c->bfgs_interrupted = 1;
+    }
+    if ((fx & FX_NEEDS_SESSION) && !c->bfgs)
+        return fail(BIOEN_HIP_ESTATE, c->bfgs_interrupted ? "the BFGS session was ended by another call on this context"
+                                                          : "no BFGS session on this context (bioen_hip_bfgs_logw_begin)");
+    if (fx & FX_DEVICE) BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------
@@ -306,6 +337,18 @@ static int h2d_user(bioen_hip_ctx* c, void* dst, const void* src, size_t bytes) 
     if (e == hipErrorInvalidValue) {
         (void)hipGetLastError();
         return h2d_staged(c, static_cast<char*>(dst), bytes, static_cast<const char*>(src), bytes, bytes, 1);
+    }
+    BIOEN_HIP_CHECK(e);
+    return 0;
+}
+
+// (a block of a caller's matrix; the mirror of d2h_user_2d below)
+static int h2d_user_2d(bioen_hip_ctx* c, void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height) {
+    const hipError_t e = staged_upload_forced() ? hipErrorInvalidValue
+                                                : hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyHostToDevice, c->stream);
+    if (e == hipErrorInvalidValue) {
+        (void)hipGetLastError();
+        return h2d_staged(c, static_cast<char*>(dst), dpitch, static_cast<const char*>(src), spitch, width, height);
     }
     BIOEN_HIP_CHECK(e);
     return 0;
@@ -596,23 +639,31 @@ static Round make_round(bioen_hip_ctx* c, const int* slots, int k, const double*
 // (the caller has produced this rank's block maxima in its X_MAX segment; they are not exchanged)
 static int enqueue_logw_adjoint(bioen_hip_ctx* c, const Round& r);
 
+// The pass family of a product with the matrix on the log-weights side, decided and made ready: *nblk > 0, the strip kernels
+// (the blocks of fwd_strip_blocks; the row-sum order copy is there in `method`'s layout, with `colsum` the column-sum order
+// one too: every copy before the first pass, so that one evaluation never mixes the two families), or *nblk = 0, the
+// streaming kernels on the row-major matrix, which is there.  A copy that cannot be allocated switches the context to the
+// streaming kernels for good (strips_unavailable).  strips_ok = false: the caller has reasons of its own against the strips.
+static int choose_logw_passes(bioen_hip_ctx* c, bool strips_ok, int method, bool colsum, int* nblk) {
+    *nblk = strips_ok ? fwd_strip_blocks(c) : 0;
+    if (*nblk > 0) {
+        int rc = ensure_strip_copy(c, method);
+        if (!rc && colsum) rc = ensure_strip_copy_colsum(c);
+        if (rc && !c->strips_unavailable) return rc;
+        if (rc) *nblk = 0;
+    }
+    return *nblk > 0 ? 0 : ensure_rowmajor(c);
+}
+
 static int enqueue_logw_eval(bioen_hip_ctx* c, const Round& r, bool with_grad) {
-    int rc;
+    int rc, nblk;
     c->last_width = r.n;
     c->last_pos = 0;
     c->last_centered = false;
     launch_logw_exp(c, r);                 // A1: e = exp(x - m_r) + prior partials (shift: this rank's own maximum)
     Vec8 w{};
     for (int a = 0; a < r.n; ++a) w.p[a] = r.w[a];
-    int nblk = fwd_strip_blocks(c);
-    if (nblk > 0) {
-        // both strip copies before the first pass, so that one evaluation never mixes the two kernel families; a
-        // copy that cannot be allocated switches the context to the streaming kernels for good (strips_unavailable)
-        rc = ensure_strip_copy(c, 0);
-        if (!rc && with_grad) rc = ensure_strip_copy_colsum(c);
-        if (rc && !c->strips_unavailable) return rc;
-        if (rc) nblk = 0;
-    }
+    if ((rc = choose_logw_passes(c, true, 0, with_grad, &nblk))) return rc;
     if (nblk > 0) {
         // matrix pass 1 streams the strip-major copy (M > 1024: row panel by row panel) straight into the matrix cores
         // (kernels_strip_logw.hip: k_strip_fwd) -- the same time for every batch width; the centre returns in
@@ -623,7 +674,6 @@ static int enqueue_logw_eval(bioen_hip_ctx* c, const Round& r, bool with_grad) {
         launch_rows_combine(c, r, true, c->strip_center, true);
         return with_grad ? enqueue_logw_adjoint(c, r) : 0;
     }
-    if ((rc = ensure_rowmajor(c))) return rc;
     launch_fwd_partial(c, r.n, w);         // A4: this rank's share of yTilde . e_a            [matrix pass 1]
     launch_fwd_rows_local(c, r.n, true);   //     + this rank's {sum e, sum e (x - G), m_r}
     if ((rc = exchange(c, X_YBAR, (size_t)ybar_payload(c, r.n, true)))) return rc;
@@ -650,6 +700,22 @@ static int enqueue_logw_adjoint(bioen_hip_ctx* c, const Round& r) {
     launch_logw_grad(c, r);                //     gradient epilogue + g.d, g.g, x.x
     if ((rc = exchange(c, X_GRAD, 3 * r.n * (size_t)vec_grid(c)))) return rc;
     launch_finish_eval(c, r);
+    return 0;
+}
+
+// One evaluation of the round's single point, start to finish: log sum exp of the prior, the point's maxima, f and (with_grad)
+// the gradient in r.g[0]; keep_point: and what the Hessian-vector products keep of it (api_hessp.inl).  -> *f; grad_out (a
+// caller's global N-vector) if given; the round's scalars in host_scal
+static int eval_logw_point(bioen_hip_ctx* c, const Round& r, bool with_grad, bool keep_point, double* f, double* grad_out) {
+    int rc;
+    if ((rc = enqueue_logs0(c, r))) return rc;
+    launch_max(c, r);
+    if ((rc = enqueue_logw_eval(c, r, with_grad))) return rc;
+    if (keep_point) launch_hessp_keep(c, c->point_fac, c->point_ybar);
+    if ((rc = check_launch())) return rc;
+    if (grad_out && (rc = download_n(c, grad_out, r.g[0]))) return rc;
+    if ((rc = read_scalars(c))) return rc;
+    if (f) *f = c->host_scal[S_F];
     return 0;
 }
 
@@ -836,6 +902,10 @@ using namespace bioen;
 // =====================================================================================
 extern "C" {
 
+// what bioen_hip_p2p_detach and bioen_hip_comm_destroy do, for the callers inside the library
+static void p2p_release(bioen_hip_ctx* c);
+static void comm_release(bioen_hip_ctx* c);
+
 const char* bioen_hip_version(void) { return "bioen_hip 0.1 (gfx950)"; }
 
 int bioen_hip_device_count(int* count) {
@@ -871,24 +941,16 @@ int bioen_hip_ctx_create_sharded(int m, long long n, const double* yTilde, const
     int rc = ctx_alloc(m, n, device, rank, world, &c);
     if (rc) return rc;
     // this rank's column block [col0, col0 + n_local) of the host matrix
-    hipError_t e = staged_upload_forced() ? hipErrorInvalidValue
-                                          : hipMemcpy2DAsync(c->Y, c->ld * sizeof(double), yTilde + c->col0, (size_t)n * sizeof(double),
-                                                             (size_t)c->n * sizeof(double), (size_t)m, hipMemcpyHostToDevice, c->stream);
-    if (e == hipErrorInvalidValue) {            // (h2d_staged: a caller's buffer the runtime will not pin)
-        (void)hipGetLastError();
-        if (h2d_staged(c, reinterpret_cast<char*>(c->Y), c->ld * sizeof(double), reinterpret_cast<const char*>(yTilde + c->col0),
-                       (size_t)n * sizeof(double), (size_t)c->n * sizeof(double), (size_t)m)) {
-            bioen_hip_ctx_destroy(c);
-            return BIOEN_HIP_EHIP;
-        }
-        e = hipSuccess;
+    rc = h2d_user_2d(c, c->Y, c->ld * sizeof(double), yTilde + c->col0, (size_t)n * sizeof(double), (size_t)c->n * sizeof(double),
+                     (size_t)m);
+    if (!rc) {
+        hipError_t e = hipMemcpyAsync(c->YT, YTilde, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "upload of yTilde", __FILE__, __LINE__);
     }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(c->YT, YTilde, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
+    if (rc) {
         bioen_hip_ctx_destroy(c);
-        return hip_fail(e, "upload of yTilde", __FILE__, __LINE__);
+        return rc;
     }
     *ctx = c;
     return 0;
@@ -915,14 +977,8 @@ int bioen_hip_ctx_create_raw(int m, long long n, int structure_major, const doub
     if (e == hipSuccess) e = hipMemcpyAsync(sigma, exp_err, (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->YT, yt.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && !structure_major) {
-        e = staged_upload_forced() ? hipErrorInvalidValue
-                                   : hipMemcpy2DAsync(c->Y, c->ld * sizeof(double), sim, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
-                                                      (size_t)m, hipMemcpyHostToDevice, c->stream);
-        if (e == hipErrorInvalidValue) {        // (h2d_staged: a caller's buffer the runtime will not pin)
-            (void)hipGetLastError();
-            e = h2d_staged(c, reinterpret_cast<char*>(c->Y), c->ld * sizeof(double), reinterpret_cast<const char*>(sim),
-                           (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)m) ? hipErrorUnknown : hipSuccess;
-        }
+        e = h2d_user_2d(c, c->Y, c->ld * sizeof(double), sim, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)m)
+                ? hipErrorUnknown : hipSuccess;
         if (e == hipSuccess) launch_rows_div(c, sigma);
     } else if (e == hipSuccess) {
         const long long chunk = std::max<long long>(1, std::min<long long>(n, (256ll << 20) / ((long long)m * 8)));
@@ -983,26 +1039,26 @@ int bioen_hip_ctx_create_synthetic(int m, int n, const double* YTrue, const doub
 }
 
 int bioen_hip_ctx_set_exchange_callback(bioen_hip_ctx* c, bioen_hip_exchange_fn fn, void* user) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     c->exchange_cb = fn;
     c->exchange_user = user;
     return 0;
 }
 
 int bioen_hip_ctx_set_force_exchange(bioen_hip_ctx* c, int on) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     c->force_exchange = on ? 1 : 0;
     return 0;
 }
 
 int bioen_hip_ctx_set_mirror_exchange(bioen_hip_ctx* c, int on) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     c->mirror_exchange = on ? 1 : 0;
     return 0;
 }
 
 int bioen_hip_exchange_counts(const bioen_hip_ctx* c, long long* rccl, long long* host_staged) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     if (rccl) *rccl = c->n_rccl_exchanges;
     if (host_staged) *host_staged = c->n_host_exchanges;
     return 0;
@@ -1010,7 +1066,7 @@ int bioen_hip_exchange_counts(const bioen_hip_ctx* c, long long* rccl, long long
 
 int bioen_hip_ctx_shard(const bioen_hip_ctx* c, int* rank, int* world, long long* n_global, long long* col0,
                         int* n_local) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     if (rank) *rank = c->rank;
     if (world) *world = c->world;
     if (n_global) *n_global = c->n_global;
@@ -1036,8 +1092,8 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     bfgs_free(c);
     hessp_free(c);
-    bioen_hip_p2p_detach(c);
-    bioen_hip_comm_destroy(c);
+    p2p_release(c);
+    comm_release(c);
     resolve_timers(c);
     for (auto& p : c->timer.pool) {
         hipEventDestroy(p.a);
@@ -1080,18 +1136,18 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
 }
 
 int bioen_hip_ctx_shape(const bioen_hip_ctx* c, int* m, int* n) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     if (m) *m = c->m;
     if (n) *n = c->n;
     return 0;
 }
 
 int bioen_hip_ctx_read_ytilde(bioen_hip_ctx* c, int row0, int rows, int col0, int cols, double* out) {
-    if (!c || !out) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
+    if (!out) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     // (col0 is relative to this context's own column block when the matrix is sharded)
     if (row0 < 0 || col0 < 0 || rows <= 0 || cols <= 0 || row0 + rows > c->m || col0 + cols > c->n)
         return fail(BIOEN_HIP_EINVAL, "block out of range");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     if (c->Y) {
         BIOEN_HIP_CHECK(d2h_user_2d(c->stream, reinterpret_cast<char*>(out), (size_t)cols * sizeof(double),
                                     reinterpret_cast<const char*>(c->Y + (size_t)row0 * c->ld + col0), c->ld * sizeof(double),
@@ -1121,7 +1177,7 @@ int bioen_hip_ctx_read_ytilde(bioen_hip_ctx* c, int row0, int rows, int col0, in
 }
 
 int bioen_hip_ctx_layout(const bioen_hip_ctx* c, int* one_copy, int* interleave, int* relayouts) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     if (one_copy) *one_copy = c->one_copy;
     if (interleave) *interleave = std::max(1, c->strip_ilv);
     if (relayouts) *relayouts = c->strip_relayouts;
@@ -1129,7 +1185,7 @@ int bioen_hip_ctx_layout(const bioen_hip_ctx* c, int* one_copy, int* interleave,
 }
 
 int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     const long long rowmajor = (long long)c->mp * (long long)c->ld * 8;
     int f = 0;
     long long b = 0;
@@ -1157,18 +1213,15 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
 }
 
 int bioen_hip_ctx_set_ytilde_target(bioen_hip_ctx* c, const double* YTilde) {
-    point_drop(c, "the targets were changed (bioen_hip_ctx_set_ytilde_target)");
-    if (!c || !YTilde) return fail(BIOEN_HIP_EINVAL, "NULL argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_CHANGES_MATRIX, __func__)) return rc;
+    if (!YTilde) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     BIOEN_HIP_CHECK(hipMemcpyAsync(c->YT, YTilde, (size_t)c->m * sizeof(double), hipMemcpyHostToDevice, c->stream));
     BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 int bioen_hip_ctx_set_affine(bioen_hip_ctx* c, const double* row_offset, const double* row_scale) {
-    point_drop(c, "the affine model was changed (bioen_hip_ctx_set_affine)");
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_CHANGES_MATRIX, __func__)) return rc;
     std::vector<double> off(c->mp, 0.0), sc(c->mp, 1.0);
     bool affine = false;
     for (int i = 0; i < c->m; ++i) {
@@ -1186,9 +1239,8 @@ int bioen_hip_ctx_set_affine(bioen_hip_ctx* c, const double* row_offset, const d
 }
 
 int bioen_hip_ctx_set_storage(bioen_hip_ctx* c, int format) {
-    point_drop(c, "the storage format was changed (bioen_hip_ctx_set_storage)");
-    if (!c || format < 0 || format > 2) return fail(BIOEN_HIP_EINVAL, "format must be 0 (FP64), 1 (fp32 + bf16 split) or 2 (fp32)");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_CHANGES_MATRIX, __func__)) return rc;
+    if (format < 0 || format > 2) return fail(BIOEN_HIP_EINVAL, "format must be 0 (FP64), 1 (fp32 + bf16 split) or 2 (fp32)");
     if (format != 0 && c->mp > 1024) return fail(BIOEN_HIP_ESTATE, "the reduced-storage experiment serves M <= 1024");
     const int rc = set_storage_format(c, format);
     if (rc == BIOEN_HIP_ESTATE) return fail(rc, "no form of the matrix to build the copies from");
@@ -1196,8 +1248,7 @@ int bioen_hip_ctx_set_storage(bioen_hip_ctx* c, int format) {
 }
 
 int bioen_hip_ctx_set_one_copy(bioen_hip_ctx* c, int on) {
-    point_drop(c, "the strip form was changed (bioen_hip_ctx_set_one_copy)");
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_DROPS_POINT, __func__)) return rc;
     if (on && c->Ys1[0]) return fail(BIOEN_HIP_ESTATE, "the column-sum order copy exists already: ask before the first gradient evaluation");
     if (!on && c->one_copy) {        // back to two copies: the second one is built at the next gradient evaluation
         c->one_copy = 0;
@@ -1207,23 +1258,22 @@ int bioen_hip_ctx_set_one_copy(bioen_hip_ctx* c, int on) {
 }
 
 int bioen_hip_ctx_set_direction_mode(bioen_hip_ctx* c, int mode) {
-    if (!c || mode < 0 || mode > 2) return fail(BIOEN_HIP_EINVAL, "mode must be 0 (auto), 1 (two-loop) or 2 (Gram form)");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
+    if (mode < 0 || mode > 2) return fail(BIOEN_HIP_EINVAL, "mode must be 0 (auto), 1 (two-loop) or 2 (Gram form)");
     c->direction_mode = mode;
     return 0;
 }
 
 int bioen_hip_synchronize(bioen_hip_ctx* c) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
     BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 // ---- log-weights ----------------------------------------------------------------------
 int bioen_hip_logw_weights(bioen_hip_ctx* c, const double* g, double* w, double* log_s) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
-    if (!c || !g) return fail(BIOEN_HIP_EINVAL, "NULL argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
+    if (!g) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     ProblemSlot& s0 = c->slot[0];
     int rc = upload_n(c, s0.x, g);
     if (rc) return rc;
@@ -1244,24 +1294,15 @@ int bioen_hip_logw_weights(bioen_hip_ctx* c, const double* g, double* w, double*
 
 int bioen_hip_logw_fdf(bioen_hip_ctx* c, const double* g, const double* G, double theta, double* f,
                        double* grad) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
-    if (!c || !g || !G) return fail(BIOEN_HIP_EINVAL, "NULL argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
+    if (!g || !G) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     ProblemSlot& s0 = c->slot[0];
     int rc;
     if ((rc = upload_n(c, s0.x, g))) return rc;
     if ((rc = upload_n(c, c->fixed, G))) return rc;
     if (grad) BIOEN_HIP_CHECK(hipMemsetAsync(s0.d, 0, c->ld * sizeof(double), c->stream));
     const int one[1] = {0};
-    const Round r = make_round(c, one, 1, nullptr, &theta);
-    if ((rc = enqueue_logs0(c, r))) return rc;
-    launch_max(c, r);
-    if ((rc = enqueue_logw_eval(c, r, grad != nullptr))) return rc;
-    if ((rc = check_launch())) return rc;
-    if (grad && (rc = download_n(c, grad, s0.g))) return rc;
-    if ((rc = read_scalars(c))) return rc;
-    if (f) *f = c->host_scal[S_F];
-    return 0;
+    return eval_logw_point(c, make_round(c, one, 1, nullptr, &theta), grad != nullptr, false, f, grad);
 }
 
 namespace {
@@ -1320,12 +1361,11 @@ int bioen_hip_opt_lbfgs_logw_batch(bioen_hip_ctx* c, int ntheta, const double* t
                                    size_t g0_stride, const double* G, const bioen_lbfgs_config* config,
                                    const bioen_visual_params* visual, int max_batch, double* results,
                                    double* w_opt, bioen_opt_result* infos) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
-    if (!c || !thetas || !g0 || !G || !config || !results || !infos || ntheta <= 0)
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
+    if (!thetas || !g0 || !G || !config || !results || !infos || ntheta <= 0)
         return fail(BIOEN_HIP_EINVAL, "NULL argument or ntheta <= 0");
     if (g0_stride != 0 && g0_stride < (size_t)c->n_global)
         return fail(BIOEN_HIP_EINVAL, "g0_stride must be 0 or >= n");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     const bool verbose = visual && visual->verbose;
     if (verbose) {
         std::printf("L-BFGS minimizer (%d theta value%s, up to %d per matrix pass)\n", ntheta, ntheta > 1 ? "s" : "",
@@ -1343,7 +1383,7 @@ int bioen_hip_opt_lbfgs_logw_batch(bioen_hip_ctx* c, int ntheta, const double* t
 int bioen_hip_opt_lbfgs_logw(bioen_hip_ctx* c, const double* g0, const double* G, double theta,
                              const bioen_lbfgs_config* config, const bioen_visual_params* visual,
                              double* result, double* w_opt, bioen_opt_result* info) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
     if (!info) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     return bioen_hip_opt_lbfgs_logw_batch(c, 1, &theta, g0, 0, G, config, visual, 1, result, w_opt, info);
 }
@@ -1366,31 +1406,49 @@ static int forces_guard(const bioen_hip_ctx* c, bool strip_path_ok = true) {
     return 0;
 }
 
+// k evaluations that share every matrix pass (slots 0 .. k-1); forces [k][m], grad [k][m]
+static int forces_eval(bioen_hip_ctx* c, int k, const double* forces, const double* w0, const double* thetas, double* f,
+                       double* grad) {
+    int rc = forces_guard(c);
+    if (rc) return rc;
+    for (int s = 0; s < k; ++s)
+        if ((rc = alloc_slot(c, s, false))) return rc;
+    if ((rc = upload_n(c, c->fixed, w0))) return rc;
+    bioen_lbfgs_config dummy{};
+    ForcesBatchEngine eng(c, dummy, false);
+    int slots[kMaxBatch];
+    const double* pt[kMaxBatch];
+    for (int a = 0; a < k; ++a) {
+        slots[a] = a;
+        pt[a] = forces + (size_t)a * c->m;
+    }
+    eng.evaluate(slots, k, pt, thetas, grad != nullptr);
+    if (eng.rc) return eng.rc;
+    for (int a = 0; a < k; ++a) {
+        if (grad)
+            for (int i = 0; i < c->m; ++i) grad[(size_t)a * c->m + i] = eng.gm_h[(size_t)i * k + a];
+        if (f) f[a] = c->host_scal[(size_t)a * kScalStride + S_F];
+    }
+    if (k > 1) c->last_width = 0;
+    return 0;
+}
+
 int bioen_hip_forces_weights(bioen_hip_ctx* c, const double* forces, const double* w0, double* w) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
-    if (!c || !forces || !w0 || !w) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
+    if (!forces || !w0 || !w) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     int rc;
     if (forces_canonical(c) && !c->storage) {
         // r05: the first half of an evaluation IS _get_weights_from_forces -- x = yTilde^T f, the softmax over all
         // structures merged segment by segment -- so sharded contexts serve the call too (one stage exchange), and every rank
         // count returns the single-GPU bits
-        if ((rc = forces_guard(c))) return rc;
-        BIOEN_HIP_CHECK(hipSetDevice(c->device));
-        if ((rc = upload_n(c, c->fixed, w0))) return rc;
-        bioen_lbfgs_config dummy{};
-        ForcesBatchEngine eng(c, dummy, false);
-        const int one[1] = {0};
-        const double* pt[1] = {forces};
         const double theta0 = 0.0;
-        eng.evaluate(one, 1, pt, &theta0, false);          // an f-only evaluation hands out the weights (slot 0)
-        if (eng.rc) return eng.rc;
+        if ((rc = forces_eval(c, 1, forces, w0, &theta0, nullptr, nullptr))) return rc;      // an f-only evaluation hands out the weights (slot 0)
         if ((rc = download_n(c, w, c->slot[0].w))) return rc;
         BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
         return transport_error(c);
     }
     rc = forces_guard(c, false);              // streaming kernels (no strip copies): unsharded contexts only
     if (rc) return rc;
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     if ((rc = upload_n(c, c->fixed, w0))) return rc;
     BIOEN_HIP_CHECK(hipMemcpyAsync(c->um, forces, (size_t)c->m * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const int one[1] = {0};
@@ -1403,25 +1461,13 @@ int bioen_hip_forces_weights(bioen_hip_ctx* c, const double* forces, const doubl
 
 int bioen_hip_forces_fdf(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* f,
                          double* grad) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
-    if (!c || !forces || !w0) return fail(BIOEN_HIP_EINVAL, "NULL argument");
-    int rc = forces_guard(c);
-    if (rc) return rc;
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
-    if ((rc = upload_n(c, c->fixed, w0))) return rc;
-    bioen_lbfgs_config dummy{};
-    ForcesBatchEngine eng(c, dummy, false);
-    const int one[1] = {0};
-    const double* pt[1] = {forces};
-    eng.evaluate(one, 1, pt, &theta, grad != nullptr);
-    if (eng.rc) return eng.rc;
-    if (grad) std::memcpy(grad, eng.gm_h, (size_t)c->m * sizeof(double));
-    if (f) *f = c->host_scal[S_F];
-    return 0;
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
+    if (!forces || !w0) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    return forces_eval(c, 1, forces, w0, &theta, f, grad);
 }
 
 int bioen_hip_speculation_stats(bioen_hip_ctx* c, long long* issued, long long* adopted) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     if (issued) *issued = c->spec_launched;
     if (adopted) *adopted = c->spec_used;
     return 0;
@@ -1429,7 +1475,7 @@ int bioen_hip_speculation_stats(bioen_hip_ctx* c, long long* issued, long long* 
 
 // diagnostic builds (-DSTRIP_DIAG=4): phase-cycle sums of the last forces strip launch, [blocks][16][8]
 int bioen_hip_debug_strip_stamps(bioen_hip_ctx* c, int enable, long long* out, int nblocks) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
     const size_t cnt = (size_t)kPartStride * 16 * 8;
     if (enable && !c->strip_stamps) {
         int rc = dalloc_zero(&c->strip_stamps, cnt, c->stream);
@@ -1445,10 +1491,9 @@ int bioen_hip_debug_strip_stamps(bioen_hip_ctx* c, int enable, long long* out, i
 // Measurement aid (tools/pass_probe.py): the two log-weights matrix passes alone, `reps` launches each at batch width k on
 // whatever the slots' vectors hold, timed with events on the context's stream.  No result is produced or changed.
 int bioen_hip_debug_pass_probe(bioen_hip_ctx* c, int k, int reps, double* fwd_ms, double* adj_ms) {
-    point_drop(c, "the pass probe ran on the slots (bioen_hip_debug_pass_probe)");
-    if (!c || !fwd_ms || !adj_ms || reps <= 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
+    if (int rc = enter(c, FX_CHANGES_MATRIX, __func__)) return rc;
+    if (!fwd_ms || !adj_ms || reps <= 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
     if (k < 1 || k > kMaxBatch) return fail(BIOEN_HIP_EINVAL, "k must be in [1, 8]");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     int rc;
     for (int s = 0; s < k; ++s)
         if ((rc = alloc_slot(c, s, false))) return rc;
@@ -1491,45 +1536,22 @@ int bioen_hip_debug_pass_probe(bioen_hip_ctx* c, int k, int reps, double* fwd_ms
 
 int bioen_hip_forces_fdf_batch(bioen_hip_ctx* c, int k, const double* forces, const double* w0, const double* thetas,
                                double* f, double* grad) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
-    if (!c || !forces || !w0 || !thetas) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
+    if (!forces || !w0 || !thetas) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (k < 1 || k > kMaxBatch) return fail(BIOEN_HIP_EINVAL, "k must be in [1, 8]");
-    int rc = forces_guard(c);
-    if (rc) return rc;
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
-    for (int s = 0; s < k; ++s)
-        if ((rc = alloc_slot(c, s, false))) return rc;
-    if ((rc = upload_n(c, c->fixed, w0))) return rc;
-    bioen_lbfgs_config dummy{};
-    ForcesBatchEngine eng(c, dummy, false);
-    int slots[kMaxBatch];
-    const double* pt[kMaxBatch];
-    for (int a = 0; a < k; ++a) {
-        slots[a] = a;
-        pt[a] = forces + (size_t)a * c->m;
-    }
-    eng.evaluate(slots, k, pt, thetas, grad != nullptr);
-    if (eng.rc) return eng.rc;
-    for (int a = 0; a < k; ++a) {
-        if (grad)
-            for (int i = 0; i < c->m; ++i) grad[(size_t)a * c->m + i] = eng.gm_h[(size_t)i * k + a];
-        if (f) f[a] = c->host_scal[(size_t)a * kScalStride + S_F];
-    }
-    if (k > 1) c->last_width = 0;
-    return 0;
+    return forces_eval(c, k, forces, w0, thetas, f, grad);
 }
 
 int bioen_hip_opt_lbfgs_forces_batch(bioen_hip_ctx* c, int ntheta, const double* thetas, const double* forces0,
                                      size_t f0_stride, const double* w0, const bioen_lbfgs_config* config,
                                      const bioen_visual_params* visual, int max_batch, double* results,
                                      double* w_opt, bioen_opt_result* infos) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
-    if (!c || !thetas || !forces0 || !w0 || !config || !results || !infos || ntheta <= 0)
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
+    if (!thetas || !forces0 || !w0 || !config || !results || !infos || ntheta <= 0)
         return fail(BIOEN_HIP_EINVAL, "NULL argument or ntheta <= 0");
     if (f0_stride != 0 && f0_stride < (size_t)c->m) return fail(BIOEN_HIP_EINVAL, "f0_stride must be 0 or >= m");
     int rc = forces_guard(c);
     if (rc) return rc;
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     const bool verbose = visual && visual->verbose;
     if (verbose) {
         std::printf("L-BFGS minimizer (forces, %d theta value%s, up to %d per matrix pass)\n", ntheta,
@@ -1546,7 +1568,7 @@ int bioen_hip_opt_lbfgs_forces_batch(bioen_hip_ctx* c, int ntheta, const double*
 int bioen_hip_opt_lbfgs_forces(bioen_hip_ctx* c, const double* forces0, const double* w0, double theta,
                                const bioen_lbfgs_config* config, const bioen_visual_params* visual,
                                double* result, double* w_opt, bioen_opt_result* info) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
     if (!info) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     // one problem; the batch width left over serves its line search's speculative trials (engine_forces.inl)
     return bioen_hip_opt_lbfgs_forces_batch(c, 1, &theta, forces0, 0, w0, config, visual, kMaxBatch, result, w_opt, info);
@@ -1554,9 +1576,8 @@ int bioen_hip_opt_lbfgs_forces(bioen_hip_ctx* c, const double* forces0, const do
 
 // ---- shared ---------------------------------------------------------------------------
 int bioen_hip_chi_squared(bioen_hip_ctx* c, const double* w, double* yave, double* chi2) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
-    if (!c || !w) return fail(BIOEN_HIP_EINVAL, "NULL argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
+    if (!w) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     ProblemSlot& s0 = c->slot[0];
     int rc;
     if ((rc = upload_n(c, s0.w, w))) return rc;       // sharded: this rank's block of the (global) w
@@ -1567,18 +1588,15 @@ int bioen_hip_chi_squared(bioen_hip_ctx* c, const double* w, double* yave, doubl
     c->last_centered = false;
     Vec8 v{};
     v.p[0] = s0.w;
-    int nblk = fwd_strip_blocks(c);
-    if (c->mp > 1024 && !c->Ys[0]) nblk = 0;      // row panels are built for the optimizer's passes, not for one product
-    if (c->storage) nblk = 0;                     // reduced-storage experiment: its copies are pre-centred; the FP64 matrix serves
-    if (nblk > 0 && (rc = ensure_strip_copy(c))) {
-        if (!c->strips_unavailable) return rc;
-        nblk = 0;
-    }
+    // not on the strips: row panels are built for the optimizer's passes, not for one product; the copies of the reduced-storage
+    // experiment are pre-centred (the FP64 matrix serves)
+    const bool strips_ok = !(c->mp > 1024 && !c->Ys[0]) && !c->storage;
+    int nblk;
+    if ((rc = choose_logw_passes(c, strips_ok, -1, false, &nblk))) return rc;
     if (nblk > 0) {            // the strip copy, uncentred (any w, not only normalised ones)
         launch_fwd_strip(c, 1, v, true);
         launch_fwd_rows_local(c, 1, false, nblk, true);
     } else {
-        if ((rc = ensure_rowmajor(c))) return rc;
         launch_fwd_partial(c, 1, v);
         launch_fwd_rows_local(c, 1, false);
     }
@@ -1594,8 +1612,7 @@ int bioen_hip_chi_squared(bioen_hip_ctx* c, const double* w, double* yave, doubl
 }
 
 int bioen_hip_last_average(bioen_hip_ctx* c, double* yraw, double* yeff) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "NULL argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
     if (c->last_width <= 0)
         return fail(BIOEN_HIP_ESTATE, "no single-problem call to take the averages from (a multi-problem call ran last)");
     std::vector<double> raw((size_t)c->m), off((size_t)c->m), sc((size_t)c->m), cen;
@@ -1635,8 +1652,8 @@ int bioen_hip_selftest_lbfgs(int kind, int n, const double* x0, const bioen_lbfg
 
 // ---- measurement ------------------------------------------------------------------------
 int bioen_hip_kernel_stats(bioen_hip_ctx* c, int which, double* total_ms, long long* launches) {
-    if (!c || which < 0 || which >= kTimerKinds) return fail(BIOEN_HIP_EINVAL, "bad argument");
-    hipSetDevice(c->device);
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
+    if (which < 0 || which >= kTimerKinds) return fail(BIOEN_HIP_EINVAL, "bad argument");
     hipStreamSynchronize(c->stream);
     resolve_timers(c);
     if (total_ms) *total_ms = c->timer.total_ms[which];
@@ -1646,15 +1663,14 @@ int bioen_hip_kernel_stats(bioen_hip_ctx* c, int which, double* total_ms, long l
 
 int bioen_hip_kernel_stats_ex(bioen_hip_ctx* c, int which, double* total_ms, long long* launches,
                               long long* problem_passes) {
-    int rc = bioen_hip_kernel_stats(c, which, total_ms, launches);
-    if (rc) return rc;
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
+    if (int rc = bioen_hip_kernel_stats(c, which, total_ms, launches)) return rc;
     if (problem_passes) *problem_passes = c->timer.problem_passes[which];
     return 0;
 }
 
 int bioen_hip_kernel_stats_reset(bioen_hip_ctx* c) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
-    hipSetDevice(c->device);
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
     hipStreamSynchronize(c->stream);
     resolve_timers(c);
     for (int i = 0; i < kTimerKinds; ++i) {
@@ -1666,7 +1682,7 @@ int bioen_hip_kernel_stats_reset(bioen_hip_ctx* c) {
 }
 
 int bioen_hip_kernel_stats_enable(bioen_hip_ctx* c, int enable) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     c->timer.enabled = enable != 0;
     return 0;
 }
@@ -1767,13 +1783,13 @@ int bioen_hip_comm_unique_id(unsigned char id[128]) {
 }
 
 int bioen_hip_comm_init(bioen_hip_ctx* c, const unsigned char id[128], int rank, int nranks) {
-    if (!c || !id || nranks <= 0 || rank < 0 || rank >= nranks) return fail(BIOEN_HIP_EINVAL, "bad argument");
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
+    if (!id || nranks <= 0 || rank < 0 || rank >= nranks) return fail(BIOEN_HIP_EINVAL, "bad argument");
     if (c->comm) return fail(BIOEN_HIP_ESTATE, "communicator already initialised");
     if (c->world > 1 && (rank != c->rank || nranks != c->world))
         return fail(BIOEN_HIP_EINVAL, "communicator rank/size must match the context's shard");
     int rc = load_rccl();
     if (rc) return rc;
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     ncclUniqueId u;
     std::memcpy(u.internal, id, 128);
     // ncclCommInitRank is a collective of all ranks and has no time limit of its own: a rank that never calls it (it failed
@@ -1843,9 +1859,9 @@ int bioen_hip_comm_init(bioen_hip_ctx* c, const unsigned char id[128], int rank,
 int bioen_hip_comm_init_abandoned(void) { return g_comm_init_abandoned.load() > 0 ? 1 : 0; }
 
 int bioen_hip_comm_allgather(bioen_hip_ctx* c, const double* send, size_t count, double* recv) {
-    if (!c || !send || !recv || count == 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
+    if (!send || !recv || count == 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
     if (!c->comm) return fail(BIOEN_HIP_ESTATE, "communicator not initialised");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     const size_t need = count * (size_t)(c->comm_nranks + 1);
     if (c->comm_buf_count < need) {
         if (c->comm_buf) hipFree(c->comm_buf);
@@ -1870,9 +1886,9 @@ int bioen_hip_comm_allgather(bioen_hip_ctx* c, const double* send, size_t count,
 }
 
 int bioen_hip_exchange_probe(bioen_hip_ctx* c, size_t count, int reps, double* usec_per_exchange) {
-    if (!c || !usec_per_exchange || reps <= 0 || count == 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
+    if (!usec_per_exchange || reps <= 0 || count == 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
     if (count > c->xcap[X_YBAR]) count = c->xcap[X_YBAR];
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     int rc = 0;
     for (int i = 0; i < 5 && !rc; ++i) rc = exchange_raw(c, X_YBAR, count);   // warm-up (connection set-up)
     if (rc) return rc;
@@ -1887,8 +1903,8 @@ int bioen_hip_exchange_probe(bioen_hip_ctx* c, size_t count, int reps, double* u
 }
 
 int bioen_hip_exchange_selftest(bioen_hip_ctx* c, int reps, long long* mismatches) {
-    if (!c || !mismatches || reps <= 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
+    if (!mismatches || reps <= 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
     unsigned long long* bad = nullptr;
     BIOEN_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&bad), sizeof *bad));
     hipError_t e = hipMemsetAsync(bad, 0, sizeof *bad, c->stream);
@@ -1921,8 +1937,8 @@ int bioen_hip_exchange_selftest(bioen_hip_ctx* c, int reps, long long* mismatche
 }
 
 int bioen_hip_read_probe(bioen_hip_ctx* c, int form, int reps, double* gbytes_per_s, long long* bytes) {
-    if (!c || !gbytes_per_s || reps <= 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
+    if (!gbytes_per_s || reps <= 0) return fail(BIOEN_HIP_EINVAL, "bad argument");
     // form: 0 = whichever is resident (strip copy first), 1 = row-major, 2 = row-sum strips, 4 = column-sum strips
     // (the strip copies are kept as row panels of <= 1024 rows: the first panel stands for the form)
     const double* ys = c->Ys[0];
@@ -1959,9 +1975,9 @@ int bioen_hip_read_probe(bioen_hip_ctx* c, int form, int reps, double* gbytes_pe
 
 // ---- peer-to-peer stage exchange (kernels_p2p.hip) ------------------------------------------------------------
 int bioen_hip_p2p_export(bioen_hip_ctx* c, unsigned char handle[64]) {
-    if (!c || !handle) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
+    if (!handle) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     if (c->p2p_on) return fail(BIOEN_HIP_ESTATE, "peer-to-peer exchange already attached");
     if (!c->p2p_box) {
         size_t cap = 0;
@@ -1993,8 +2009,12 @@ int bioen_hip_p2p_export(bioen_hip_ctx* c, unsigned char handle[64]) {
 }
 
 int bioen_hip_p2p_detach(bioen_hip_ctx* c) {
-    if (!c) return 0;
-    hipSetDevice(c->device);
+    if (int rc = enter(c, FX_DEVICE, __func__)) return c ? rc : 0;      // (NULL: nothing to detach)
+    p2p_release(c);
+    return 0;
+}
+
+static void p2p_release(bioen_hip_ctx* c) {      // (the context's device is the current one)
     if (c->stream) hipStreamSynchronize(c->stream);
     c->p2p_on = 0;
     if (c->failed_p2p) {     // the failure was this transport's own; the stream has drained and the transport goes: the
@@ -2019,12 +2039,11 @@ int bioen_hip_p2p_detach(bioen_hip_ctx* c) {
     c->p2p_cnt = nullptr;
     c->p2p_seq = 0;
     (void)hipGetLastError();
-    return 0;
 }
 
 int bioen_hip_p2p_attach(bioen_hip_ctx* c, const unsigned char* handles) {
-    if (!c || (!handles && c->world > 1)) return fail(BIOEN_HIP_EINVAL, "NULL argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_DEVICE, __func__)) return rc;
+    if (!handles && c->world > 1) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (c->p2p_on) return fail(BIOEN_HIP_ESTATE, "peer-to-peer exchange already attached");
     if (!c->p2p_box) return fail(BIOEN_HIP_ESTATE, "bioen_hip_p2p_export first");
     std::vector<double*> peers((size_t)c->world, nullptr);
@@ -2080,9 +2099,7 @@ int bioen_hip_p2p_attach(bioen_hip_ctx* c, const unsigned char* handles) {
         if (e != hipSuccess) rc = hip_fail(e, "peer table", __FILE__, __LINE__);
     }
     if (rc) {
-        const std::string keep = g_last_error;
-        bioen_hip_p2p_detach(c);
-        g_last_error = keep;
+        p2p_release(c);      // (reports nothing: the failure's message stays)
         return rc;
     }
     c->p2p_seq = 0;
@@ -2091,7 +2108,7 @@ int bioen_hip_p2p_attach(bioen_hip_ctx* c, const unsigned char* handles) {
 }
 
 int bioen_hip_exchange_transport(const bioen_hip_ctx* c) {
-    if (!c) return -1;
+    if (enter(c, FX_NONE, __func__)) return -1;
     if (c->p2p_on) return 3;
     if (c->comm) return 1;
     if (c->exchange_cb) return 2;
@@ -2099,7 +2116,7 @@ int bioen_hip_exchange_transport(const bioen_hip_ctx* c) {
 }
 
 int bioen_hip_exchange_counts3(const bioen_hip_ctx* c, long long* rccl, long long* host_staged, long long* p2p) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
     if (rccl) *rccl = c->n_rccl_exchanges;
     if (host_staged) *host_staged = c->n_host_exchanges;
     if (p2p) *p2p = c->n_p2p_exchanges;
@@ -2107,20 +2124,25 @@ int bioen_hip_exchange_counts3(const bioen_hip_ctx* c, long long* rccl, long lon
 }
 
 int bioen_hip_ctx_set_wait_timeout(bioen_hip_ctx* c, double seconds) {
-    if (!c || !(seconds > 0.0)) return fail(BIOEN_HIP_EINVAL, "bad argument");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
+    if (!(seconds > 0.0)) return fail(BIOEN_HIP_EINVAL, "bad argument");
     c->wait_timeout_s = seconds;
     return 0;
 }
 
 int bioen_hip_comm_destroy(bioen_hip_ctx* c) {
-    if (!c) return 0;
+    if (enter(c, FX_NONE, __func__)) return 0;      // (NULL: nothing to destroy)
+    comm_release(c);
+    return 0;
+}
+
+static void comm_release(bioen_hip_ctx* c) {
     if (c->comm && c->failed) rccl_abort(c);      // a destroy would wait for peers that may be gone
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(static_cast<ncclComm_t>(c->comm));
     c->comm = nullptr;
     if (c->comm_buf) hipFree(c->comm_buf);
     c->comm_buf = nullptr;
     c->comm_buf_count = 0;
-    return 0;
 }
 
 }  // extern "C"

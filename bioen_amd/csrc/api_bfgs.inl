@@ -10,8 +10,8 @@
 //   update  one pass over H (pending update of the previous step + row sums H [y, g]), 4 dots, the next direction
 //   end     w, chi^2, S at x; H is freed
 //
-// A session lives on an UNSHARDED context only.  Any other evaluation or optimiser call on the context ends it (its
-// next bfgs call returns BIOEN_HIP_ESTATE); so does every error inside a bfgs call, and bioen_hip_ctx_destroy.
+// A session lives on an UNSHARDED context only.  Which other calls on the context end it is each entry's declaration to
+// the guard (api.hip: enter); every error inside a bfgs call ends it too, and bioen_hip_ctx_destroy.
 
 namespace bioen {
 
@@ -45,25 +45,6 @@ static void bfgs_free(bioen_hip_ctx* c) {
     delete S;
     c->bfgs = nullptr;
     c->bfgs_hbytes = 0;
-}
-
-static void bfgs_interrupt(bioen_hip_ctx* c) {
-    point_drop(c, "another evaluation or optimizer call ran on the context");
-    if (c && c->bfgs) {
-        bfgs_free(c);
-        c->bfgs_interrupted = 1;
-    }
-}
-
-static int bfgs_session(bioen_hip_ctx* c, BfgsSession** S) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
-    point_drop(c, "a BFGS session ran on the context");
-    if (!c->bfgs)
-        return fail(BIOEN_HIP_ESTATE, c->bfgs_interrupted
-                                          ? "the BFGS session was ended by another call on this context"
-                                          : "no BFGS session on this context (bioen_hip_bfgs_logw_begin)");
-    *S = c->bfgs;
-    return 0;
 }
 
 static int bfgs_error(bioen_hip_ctx* c, int rc) {     // every error path frees H
@@ -149,13 +130,7 @@ static int bfgs_begin(bioen_hip_ctx* c, const double* g0, const double* G, doubl
     if ((rc = dalloc_zero(&S->dsc, 8, c->stream))) return rc;
     if ((rc = upload_n(c, S->x, g0))) return rc;
     if ((rc = upload_n(c, c->fixed, G))) return rc;
-    const Round r = bfgs_round(c, S, S->x, S->g);
-    if ((rc = enqueue_logs0(c, r))) return rc;
-    launch_max(c, r);
-    if ((rc = enqueue_logw_eval(c, r, true))) return rc;
-    if ((rc = check_launch())) return rc;
-    if ((rc = read_scalars(c))) return rc;
-    *f0 = c->host_scal[S_F];
+    if ((rc = eval_logw_point(c, bfgs_round(c, S, S->x, S->g), true, false, f0, nullptr))) return rc;
     const double gg = c->host_scal[S_GG];
     *gnorm2 = std::sqrt(gg);
     if (norm_inf) {
@@ -254,11 +229,10 @@ extern "C" {
 
 int bioen_hip_bfgs_logw_begin(bioen_hip_ctx* c, const double* g0, const double* G, double theta, int norm_inf,
                               double* f0, double* gnorm, double* gnorm2, double* dphi0) {
-    if (!c || !g0 || !G || !f0 || !gnorm || !gnorm2 || !dphi0) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;      // a call rejected for its arguments leaves point and session ...
+    if (!g0 || !G || !f0 || !gnorm || !gnorm2 || !dphi0) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (c->world > 1) return fail(BIOEN_HIP_ESTATE, "the BFGS session needs an unsharded context (world = 1)");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
-    point_drop(c, "a BFGS session ran on the context");
-    bfgs_free(c);
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;      // ... a valid one starts afresh
     c->bfgs_interrupted = 0;
     // memory check first: nothing is allocated for a matrix that cannot fit
     const size_t ldh = bfgs_ld(c->n);
@@ -278,41 +252,31 @@ int bioen_hip_bfgs_logw_begin(bioen_hip_ctx* c, const double* g0, const double* 
 }
 
 int bioen_hip_bfgs_logw_trial(bioen_hip_ctx* c, double alpha, int need_grad, double* f, double* dphi) {
-    BfgsSession* S = nullptr;
-    int rc = bfgs_session(c, &S);
-    if (rc) return rc;
+    if (int rc = enter(c, FX_SESSION_CALL, __func__)) return rc;
     if (!f) return fail(BIOEN_HIP_EINVAL, "NULL argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
-    rc = bfgs_trial(c, S, alpha, need_grad, f, dphi);
+    const int rc = bfgs_trial(c, c->bfgs, alpha, need_grad, f, dphi);
     return rc ? bfgs_error(c, rc) : 0;
 }
 
 int bioen_hip_bfgs_logw_accept(bioen_hip_ctx* c, double alpha, int norm_inf, double* gnorm, double* pnorm,
                                double* xnorm) {
-    BfgsSession* S = nullptr;
-    int rc = bfgs_session(c, &S);
-    if (rc) return rc;
+    if (int rc = enter(c, FX_SESSION_CALL, __func__)) return rc;
     if (!gnorm || !pnorm || !xnorm) return fail(BIOEN_HIP_EINVAL, "NULL argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
-    rc = bfgs_accept(c, S, alpha, norm_inf, gnorm, pnorm, xnorm);
+    const int rc = bfgs_accept(c, c->bfgs, alpha, norm_inf, gnorm, pnorm, xnorm);
     return rc ? bfgs_error(c, rc) : 0;
 }
 
 int bioen_hip_bfgs_logw_update(bioen_hip_ctx* c, double* dphi0, int* rho_fallback) {
-    BfgsSession* S = nullptr;
-    int rc = bfgs_session(c, &S);
-    if (rc) return rc;
+    if (int rc = enter(c, FX_SESSION_CALL, __func__)) return rc;
     if (!dphi0 || !rho_fallback) return fail(BIOEN_HIP_EINVAL, "NULL argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
-    rc = bfgs_update(c, S, dphi0, rho_fallback);
+    const int rc = bfgs_update(c, c->bfgs, dphi0, rho_fallback);
     return rc ? bfgs_error(c, rc) : 0;
 }
 
 int bioen_hip_bfgs_logw_end(bioen_hip_ctx* c, double* g_out, double* w_out, bioen_opt_result* info) {
-    BfgsSession* S = nullptr;
-    int rc = bfgs_session(c, &S);
-    if (rc) return rc;
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, FX_SESSION_CALL, __func__)) return rc;
+    BfgsSession* S = c->bfgs;
+    int rc = 0;
     do {
         const Round r = bfgs_round(c, S, S->x, S->gt);
         launch_max(c, r);
@@ -341,21 +305,19 @@ int bioen_hip_bfgs_logw_end(bioen_hip_ctx* c, double* g_out, double* w_out, bioe
 }
 
 int bioen_hip_bfgs_logw_read_hinv(bioen_hip_ctx* c, int row0, int rows, int padded, double* out) {
-    BfgsSession* S = nullptr;
-    int rc = bfgs_session(c, &S);
-    if (rc) return rc;
+    if (int rc = enter(c, FX_SESSION_CALL, __func__)) return rc;
+    BfgsSession* S = c->bfgs;
     if (!out) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     const long long height = padded ? (long long)S->ldh : (long long)c->n;      // padded: the stored rows, pads included
     if (row0 < 0 || rows <= 0 || row0 + rows > height) return fail(BIOEN_HIP_EINVAL, "rows out of range");
     const size_t width = padded ? S->ldh : (size_t)c->n;
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     double* stage = nullptr;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&stage), (size_t)rows * S->ldh * sizeof(double));
     if (e != hipSuccess) return hip_fail(e, "hipMalloc (inverse Hessian read-back)", __FILE__, __LINE__);
     const bool pend = S->ps >= 0;
     launch_bfgs_hread(c, S->H, S->ldh, !S->have_h, pend ? S->sb[S->ps] : S->sb[0], pend ? S->ub[S->pu] : S->ub[0],
                       pend ? S->rho : 0.0, pend ? S->cc : 0.0, (size_t)row0, rows, stage);
-    rc = check_launch();
+    int rc = check_launch();
     if (!rc) {
         e = d2h_user_2d(c->stream, reinterpret_cast<char*>(out), width * sizeof(double),
                         reinterpret_cast<const char*>(stage), S->ldh * sizeof(double), width * sizeof(double),
@@ -368,14 +330,12 @@ int bioen_hip_bfgs_logw_read_hinv(bioen_hip_ctx* c, int row0, int rows, int padd
 }
 
 int bioen_hip_bfgs_logw_read_vec(bioen_hip_ctx* c, int which, double* out) {
-    BfgsSession* S = nullptr;
-    int rc = bfgs_session(c, &S);
-    if (rc) return rc;
+    if (int rc = enter(c, FX_SESSION_CALL, __func__)) return rc;
+    BfgsSession* S = c->bfgs;
     if (!out || which < 0 || which > 5) return fail(BIOEN_HIP_EINVAL, "bad argument");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     const double* v[6] = {S->x, S->g, S->p, S->s_new >= 0 ? S->sb[S->s_new] : S->sb[0], S->y,
                           S->pu >= 0 ? S->ub[S->pu] : S->ub[0]};
-    if ((rc = download_n(c, out, v[which]))) return rc;
+    if (int rc = download_n(c, out, v[which])) return rc;
     BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -60,13 +60,8 @@ static int hessp_products(bioen_hip_ctx* c, int k, const double* v, double* hv) 
         sc.p[a] = h.scal[a];
     }
     // the pass family is the one enqueue_logw_eval takes on this context (the point's evaluation has built the copies)
-    int nblk = fwd_strip_blocks(c);
-    if (nblk > 0) {
-        rc = ensure_strip_copy(c, 0);
-        if (!rc) rc = ensure_strip_copy_colsum(c);
-        if (rc && !c->strips_unavailable) return rc;
-        if (rc) nblk = 0;
-    }
+    int nblk;
+    if ((rc = choose_logw_passes(c, true, 0, true, &nblk))) return rc;
     c->last_width = k;              // ybar_c: the point's raw averages in every column
     c->last_pos = 0;
     c->last_centered = false;
@@ -77,7 +72,6 @@ static int hessp_products(bioen_hip_ctx* c, int k, const double* v, double* hv) 
         launch_hessp_combine(c, h, c->strip_center);
         launch_adj_strip(c, k, c->r_c, out, sc);
     } else {
-        if ((rc = ensure_rowmajor(c))) return rc;
         launch_fwd_partial(c, k, tv);
         launch_fwd_rows_local(c, k, false);
         if ((rc = exchange(c, X_YBAR, (size_t)ybar_payload(c, k, false)))) return rc;
@@ -96,42 +90,34 @@ static int hessp_products(bioen_hip_ctx* c, int k, const double* v, double* hv) 
 
 extern "C" int bioen_hip_logw_hessp(bioen_hip_ctx* c, const double* g, const double* G, double theta, int k,
                                     const double* v, double* hv, double* f, double* grad) {
-    if (!c) return fail(BIOEN_HIP_EINVAL, "ctx is NULL");
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;      // a call rejected below leaves the point (and the device) alone ...
     if (k < 0 || k > kMaxBatch) return fail(BIOEN_HIP_EINVAL, "k must be in [0, 8]");
     if (k > 0 && (!v || !hv)) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (g && !G) return fail(BIOEN_HIP_EINVAL, "g without G");
     if (!g && !c->point_valid) {
         const std::string m = c->point_lost
-                                  ? std::string("the point of the last bioen_hip_logw_hessp call with g is gone: ") + c->point_lost
+                                  ? std::string("the point of the last bioen_hip_logw_hessp call with g is gone: dropped by ") + c->point_lost
                                   : std::string("no point on this context: call bioen_hip_logw_hessp with g first");
         return fail(BIOEN_HIP_ESTATE, m.c_str());
     }
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
+    if (int rc = enter(c, g ? FX_EVALUATES : FX_DEVICE, __func__)) return rc;      // ... with g it is an evaluation
     int rc;
     if (g) {
-        bfgs_interrupt(c);          // ends a live BFGS session, drops the point kept so far
-        c->point_lost = "a call that set a new point failed";
+        c->point_lost = "a call that failed to set a new point";
         if ((rc = hessp_buffers(c, 0))) return rc;
         ProblemSlot& s0 = c->slot[0];
         if ((rc = upload_n(c, s0.x, g))) return rc;
         if ((rc = upload_n(c, c->fixed, G))) return rc;
         BIOEN_HIP_CHECK(hipMemsetAsync(s0.d, 0, c->ld * sizeof(double), c->stream));
         const int one[1] = {0};
-        const Round r = make_round(c, one, 1, nullptr, &theta);
-        if ((rc = enqueue_logs0(c, r))) return rc;
-        launch_max(c, r);
-        if ((rc = enqueue_logw_eval(c, r, true))) return rc;      // bioen_hip_logw_fdf's evaluation, launch for launch
-        launch_hessp_keep(c, c->point_fac, c->point_ybar);
-        if ((rc = check_launch())) return rc;
-        if (grad && (rc = download_n(c, grad, s0.g))) return rc;
-        if ((rc = read_scalars(c))) return rc;
-        if (f) *f = c->host_scal[S_F];
+        // bioen_hip_logw_fdf's evaluation, launch for launch
+        if ((rc = eval_logw_point(c, make_round(c, one, 1, nullptr, &theta), true, true, f, grad))) return rc;
         c->point_theta = theta;
         c->point_valid = 1;
         c->point_lost = nullptr;
     }
     if (k == 0) return 0;
     rc = hessp_products(c, k, v, hv);
-    if (rc) point_drop(c, "a product on it failed");
+    if (rc) point_drop(c, "a product on it that failed");
     return rc;
 }

@@ -195,10 +195,9 @@ const char* bioen_hip_gsl_strerror(int code) { return multimin::status_string(co
 int bioen_hip_opt_gsl_logw(bioen_hip_ctx* c, const double* g0, const double* G, double theta,
                            const bioen_gsl_config* config, const bioen_visual_params* visual, double* result,
                            double* w_opt, bioen_opt_result* info) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
-    if (!c || !g0 || !G || !config || !result || !info) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
+    if (!g0 || !G || !config || !result || !info) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (config->algorithm < 0 || config->algorithm > 4) return fail(BIOEN_HIP_EINVAL, "unknown GSL algorithm id");
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     const bool verbose = visual && visual->verbose;
     print_gsl_config(*config, verbose);
     std::memset(info, 0, sizeof *info);
@@ -235,12 +234,11 @@ int bioen_hip_opt_gsl_logw(bioen_hip_ctx* c, const double* g0, const double* G, 
 int bioen_hip_opt_gsl_forces(bioen_hip_ctx* c, const double* forces0, const double* w0, double theta,
                              const bioen_gsl_config* config, const bioen_visual_params* visual, double* result,
                              double* w_opt, bioen_opt_result* info) {
-    bfgs_interrupt(c);          // ends a live BFGS session (api_bfgs.inl)
-    if (!c || !forces0 || !w0 || !config || !result || !info) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
+    if (!forces0 || !w0 || !config || !result || !info) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (config->algorithm < 0 || config->algorithm > 4) return fail(BIOEN_HIP_EINVAL, "unknown GSL algorithm id");
     int rc = forces_guard(c);
     if (rc) return rc;
-    BIOEN_HIP_CHECK(hipSetDevice(c->device));
     const bool verbose = visual && visual->verbose;
     print_gsl_config(*config, verbose);
     std::memset(info, 0, sizeof *info);
