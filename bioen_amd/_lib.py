@@ -102,6 +102,7 @@ _SIGNATURES = {
     "bioen_hip_speculation_stats": (C.c_int, [ctx_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "bioen_hip_debug_strip_stamps": (C.c_int, [ctx_p, C.c_int, C.POINTER(C.c_longlong), C.c_int]),
     "bioen_hip_ctx_layout": (C.c_int, [ctx_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bioen_hip_ctx_strip_plan": (C.c_int, [ctx_p, C.c_int] + [C.POINTER(C.c_int)] * 6),
     "bioen_hip_debug_pass_probe": (C.c_int, [ctx_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bioen_hip_ctx_create_raw": (C.c_int, [C.c_int, C.c_longlong, C.c_int, dp, dp, dp, C.c_int, C.POINTER(ctx_p)]),
     "bioen_hip_gsl_strerror": (C.c_char_p, [C.c_int]),
@@ -442,6 +443,15 @@ class Context(object):
         a, b, c_ = C.c_int(0), C.c_int(1), C.c_int(0)
         check(lib().bioen_hip_ctx_layout(self._h, C.byref(a), C.byref(b), C.byref(c_)))
         return {"one_copy": a.value, "interleave": b.value, "relayouts": c_.value}
+
+    def strip_plan(self, which):
+        """The regime of the strip passes' launch plan (bioen_hip_ctx_strip_plan; no device call).  which: 0 = the
+        log-weights forward pass, 1 = the forces passes.  -> {"sps": strips per segment, "gs": groups per segment (0: the
+        strip passes do not apply), "tc": strips per chunk (forces: the most strips a group runs per segment), "nch": chunks
+        per group, "fold": a slot runs a whole group, "local_segments"}"""
+        o = [C.c_int(0) for _ in range(6)]
+        check(lib().bioen_hip_ctx_strip_plan(self._h, int(which), *[C.byref(v) for v in o]))
+        return dict(zip(("sps", "gs", "tc", "nch", "fold", "local_segments"), (v.value for v in o)))
 
     def set_target(self, YTilde):
         check(lib().bioen_hip_ctx_set_ytilde_target(self._h, ptr(self._mvec(YTilde, "YTilde"))))

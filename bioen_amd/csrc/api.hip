@@ -1184,6 +1184,20 @@ int bioen_hip_ctx_layout(const bioen_hip_ctx* c, int* one_copy, int* interleave,
     return 0;
 }
 
+int bioen_hip_ctx_strip_plan(const bioen_hip_ctx* c, int pass, int* sps, int* gs, int* tc, int* nch, int* fold,
+                             int* local_segments) {
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
+    if (pass != 0 && pass != 1) return fail(BIOEN_HIP_EINVAL, "bioen_hip_ctx_strip_plan: pass is 0 (log-weights forward) or 1 (forces)");
+    const StripSets ss = pass == 0 ? strip_sets(c) : forces_sets(c);      // what the launchers take (strip_plan.cpp)
+    if (sps) *sps = ss.sps;
+    if (gs) *gs = ss.gs;
+    if (tc) *tc = ss.tc;
+    if (nch) *nch = ss.nch;
+    if (fold) *fold = ss.fold;
+    if (local_segments) *local_segments = c->vr;
+    return 0;
+}
+
 int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes) {
     if (int rc = enter(c, FX_NONE, __func__)) return rc;
     const long long rowmajor = (long long)c->mp * (long long)c->ld * 8;

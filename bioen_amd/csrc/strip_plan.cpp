@@ -47,7 +47,8 @@ static StripSets make_sets(const bioen_hip_ctx* c, int gs_nominal, bool may_fold
     ss.tc = (tmax + 7) / 8;
     ss.nch = (tmax + ss.tc - 1) / ss.tc;
     // a context that holds all eight segments runs whole groups per slot (8 x gs slots: the full grid) and adds up the
-    // chunks in registers; BIOEN_HIP_STRIP_FOLD=0: one chunk per slot there too (tests: the same bits)
+    // chunks in registers; BIOEN_HIP_STRIP_FOLD=0: one chunk per slot there too (the same bits:
+    // tests/test_hip_strip_loops.py::test_unfolded_forward_pass_gives_the_folded_bits, at chunks of two strips)
     ss.fold = (may_fold && c->vr >= 8 && env_flag("BIOEN_HIP_STRIP_FOLD", 1) != 0) ? 1 : 0;
     ss.slots = ss.gs * (ss.fold ? 1 : ss.nch);
     ss.sets = ss.slots;

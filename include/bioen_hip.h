@@ -176,6 +176,15 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* ctx, int* forms, long long* byt
  * other method starts on the context (relayouts counts the moves; results never depend on the layout).
  * BIOEN_HIP_STRIP_INTERLEAVE=0: strip order always (A/B). */
 int bioen_hip_ctx_layout(const bioen_hip_ctx* ctx, int* one_copy, int* interleave, int* relayouts);
+/* Which regime of the strip passes' launch plan this context is in (read-only: what the launchers compute, no device
+ * call).  pass 0: the log-weights forward pass, pass 1: the forces passes (gs = 0: they do not apply to this context).
+ * Per column segment: its sps strips of 16 columns are dealt to gs groups (group g: strips g, g + gs, ...), so the
+ * first sps - gs * (ceil(sps / gs) - 1) groups hold ceil(sps / gs) strips and the others one fewer.  tc: strips per chunk (forces passes: per
+ * group and segment, the larger count), nch: chunks per group, fold: 1 = a slot runs a whole group and adds its chunks up
+ * in registers, local_segments: the segments this context holds.  Any result pointer may be NULL; another pass is
+ * BIOEN_HIP_EINVAL.  For tests that must prove a slot ran several strips of a segment. */
+int bioen_hip_ctx_strip_plan(const bioen_hip_ctx* ctx, int pass, int* sps, int* gs, int* tc, int* nch, int* fold,
+                             int* local_segments);
 /* r05: ask for (1) / give up (0) the ONE-copy form described above; to be called before the context's first gradient
  * evaluation (BIOEN_HIP_ESTATE once the column-sum order copy exists).  Beyond 1024 rows it serves both methods: one set
  * of row panels instead of two.

@@ -83,6 +83,7 @@ ENTRIES = {
     "bioen_hip_ctx_shape": Row("keeps", "keeps", _shape),
     "bioen_hip_ctx_footprint": Row("keeps", "keeps", lambda c: c.footprint()),
     "bioen_hip_ctx_layout": Row("keeps", "keeps", lambda c: c.layout()),
+    "bioen_hip_ctx_strip_plan": Row("keeps", "keeps", lambda c: (c.strip_plan(0), c.strip_plan(1))),
     "bioen_hip_ctx_set_direction_mode": Row("keeps", "keeps", lambda c: c.set_direction_mode("auto")),
     "bioen_hip_ctx_set_wait_timeout": Row("keeps", "keeps", lambda c: c.set_wait_timeout(30.0)),
     "bioen_hip_kernel_stats_enable": Row("keeps", "keeps", lambda c: c.kernel_stats_enable(False)),
