@@ -459,7 +459,10 @@ class Context(object):
     def set_affine(self, row_offset=None, row_scale=None):
         """Optimise against row_offset[i] + row_scale[i] * yTilde[i][j] without touching the resident
         matrix (DEER modulation depths, SAXS scaling factor).  None -> 0 resp. 1; a scalar
-        row_scale applies to every row."""
+        row_scale applies to every row.  Both methods honour it: the log-weights evaluations, products and
+        optimizers, and every forces call (forces_weights, forces_fdf(_batch), opt_lbfgs_forces(_batch),
+        opt_gsl_forces; sharded contexts too).  (0, 1) -- or None, None -- is the plain model, bit for bit.  The
+        forces calls raise BioenHipError (invalid state) while a model AND a reduced storage format are set."""
         off = None if row_offset is None else self._mvec(row_offset, "row_offset")
         if row_scale is not None and np.ndim(row_scale) == 0:
             row_scale = np.full(self.m, float(row_scale))
@@ -667,12 +670,15 @@ class Context(object):
 
     # -- forces -------------------------------------------------------------------
     def forces_weights(self, forces, w0):
+        """w_j = w0_j exp(x_j) / Z with x = yTilde_eff^T forces -- of the affine model if one is set (set_affine)"""
         f, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
         w = np.empty(self.n)
         check(lib().bioen_hip_forces_weights(self._h, ptr(f), ptr(w0), ptr(w)))
         return w
 
     def forces_fdf(self, forces, w0, theta, need_f=True, need_grad=True):
+        """-> (f, grad[m]) of the forces objective on the resident matrix, or on row_offset + row_scale * matrix
+        where set_affine has set a model (the gradient is then the one with respect to the forces of that model)"""
         fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
         f = C.c_double(0.0)
         grad = np.empty(self.m) if need_grad else None
@@ -681,7 +687,8 @@ class Context(object):
         return (f.value if need_f else None), grad
 
     def forces_fdf_batch(self, forces, w0, thetas, need_grad=True):
-        """K <= 8 evaluations sharing every matrix pass.  forces: (K, m), thetas: (K,) -> (f[K], grad[K, m] or None)"""
+        """K <= 8 evaluations sharing every matrix pass.  forces: (K, m), thetas: (K,) -> (f[K], grad[K, m] or None).
+        Every column is the single call's result bit for bit, with or without an affine model."""
         thetas = as_f64(thetas).ravel()
         k = thetas.size
         fo = as_f64(forces).reshape(k, self.m)
@@ -693,6 +700,8 @@ class Context(object):
         return f, grad
 
     def opt_lbfgs_forces(self, forces0, w0, theta, params, verbose=False, debug=False, want_weights=True):
+        """L-BFGS on the forces objective (of the affine model if one is set) -> (forces, weights or None, OptResult);
+        last_average() then hands out the averages at the returned point (nuisance.series_forces refits on them)"""
         f0, w0 = self._mvec(forces0, "forces0"), self._nvec(w0, "w0")
         cfg = lbfgs_config(params)
         vis = VisualParams(int(bool(debug)), int(bool(verbose)))
@@ -704,6 +713,7 @@ class Context(object):
         return res, w, info
 
     def opt_gsl_forces(self, forces0, w0, theta, algorithm, params, verbose=False, debug=False, want_weights=True):
+        """the GSL-style minimizers on the forces objective (of the affine model if one is set)"""
         f0, w0 = self._mvec(forces0, "forces0"), self._nvec(w0, "w0")
         cfg = gsl_config(algorithm, params)
         vis = VisualParams(int(bool(debug)), int(bool(verbose)))
@@ -717,7 +727,8 @@ class Context(object):
     def opt_lbfgs_forces_batch(self, thetas, forces0, w0, params, max_batch=8, verbose=False, debug=False,
                                want_weights=True):
         """theta series of the forces method; up to `max_batch` (<= 8) thetas share every matrix pass.
-        forces0: (m,) shared start or (ntheta, m).  -> (forces[ntheta, m], weights[ntheta, n] or None, infos)"""
+        forces0: (m,) shared start or (ntheta, m).  -> (forces[ntheta, m], weights[ntheta, n] or None, infos).
+        An affine model (set_affine) applies to every theta of the series."""
         thetas = as_f64(thetas).ravel()
         nt = thetas.size
         f0 = as_f64(forces0)

@@ -740,6 +740,7 @@ static int enqueue_forces_weights(bioen_hip_ctx* c, const ForcesRound& fr) {    
     for (int a = 0; a < fr.n; ++a) out.p[a] = fr.a[a];
     const int rc = ensure_rowmajor(c);        // the row-major matrix (back from the strip copy if it was freed)
     if (rc) return rc;
+    if (c->affine) launch_forces_affine_operand(c, fr.n);      // um <- f o sc: x_j = sum_i f_i (off_i + sc_i Y_ij) - const
     launch_adj(c, fr.n, c->um, out, false);   // F1: x_j = sum_i f_i yTilde_ij     [matrix pass 1]
     launch_forces_max(c, fr);
     launch_forces_exp(c, fr);
@@ -747,6 +748,10 @@ static int enqueue_forces_weights(bioen_hip_ctx* c, const ForcesRound& fr) {    
     return 0;
 }
 
+// Affine observable model: the passes below run on the resident matrix as they are; three steps on M-vectors,
+// taken on such a context only, make them the evaluation on off_i + sc_i Y_ij -- the operand of pass 1 is f o sc, the
+// constant of b_j gains sum_i off_i r_i (k_rows_combine has left r o sc in r_c), and the gradient, once the segments'
+// shares are added, is multiplied by sc_i: what the host's line search and k_forces_publish read is the scaled one.
 static int enqueue_forces_eval(bioen_hip_ctx* c, const ForcesRound& fr, const Round& r, bool with_grad) {
     int nblk = forces_fused_blocks(c);
     int rc;
@@ -767,15 +772,18 @@ static int enqueue_forces_eval(bioen_hip_ctx* c, const ForcesRound& fr, const Ro
         // the same k_rows_combine), the shares of the gradient in a second one.
         // Both passes read the strip-major copy centred on the targets (strip.hpp); ybar_c then holds
         // ybar - center, the row offset of k_rows_combine puts the centre back for r, chi^2 and f.
+        if (c->affine) launch_forces_affine_operand(c, fr.n);
         launch_forces_xy(c, fr, nblk);        // F1 + F2: x, online softmax, this rank's ybar   [matrix pass 1]
         if ((rc = exchange(c, X_YBAR, (size_t)ybar_payload(c, fr.n, true)))) return rc;
         launch_rows_combine(c, r, true, c->strip_center, false);   //     normalisation, ybar (centred), r, chi^2, KL, f
         c->last_centered = true;               // ybar_c = ybar - strip_center (bioen_hip_last_average adds it back)
         if (with_grad) {
+            if (c->affine) launch_forces_affine_const(c, fr, c->strip_center, true);   // pass 2's constant: S_B0 += sum_i off_i r_i
             launch_forces_bt(c, fr);          // F3: b, t, product with t            [matrix pass 2]
             launch_fwd_rows_forces_grad_share(c, fr.n, nblk, &fr, true);   // every segment's share (one GPU: all eight)
             if ((rc = exchange(c, X_YBAR, (size_t)c->mp * fr.n))) return rc;
             launch_forces_grad_sum_ranks(c, fr.n);                         // ... added in segment order
+            if (c->affine) launch_forces_affine_grad(c, fr.n);
         } else {
             launch_forces_w_from_x(c, fr);    // f-only evaluations hand out the weights
         }
@@ -805,6 +813,7 @@ static int enqueue_forces_eval(bioen_hip_ctx* c, const ForcesRound& fr, const Ro
             v.p[a] = fr.w[a];
         }
         const StripSets ss = strip_sets(c);
+        if (c->affine) launch_forces_affine_operand(c, fr.n);
         launch_adj_strip(c, fr.n, c->um, out, MVec8{}, true);          // F1: x_j = sum_i f_i yTilde_ij   [matrix pass 1]
         launch_max(c, rx);                                             //     block maxima of x per segment
         launch_forces_seg_exp(c, fr);                                  //     e = w0 exp(x - m_v) -> w ; shares of sum e, sum e x
@@ -815,6 +824,7 @@ static int enqueue_forces_eval(bioen_hip_ctx* c, const ForcesRound& fr, const Ro
         c->last_centered = true;
         launch_scale_w(c, r);                                          //     w = e S_INV[v]: the weights
         if (with_grad) {
+            if (c->affine) launch_forces_affine_const(c, fr, c->strip_center, false);   // S_OR: k_forces_seg_t adds it to b
             launch_adj_strip(c, fr.n, c->r_c, out, MVec8{}, true);          // F3: b = yTilde^T r  [matrix pass 3]
             launch_forces_seg_t(c, fr, ss.gs * (ss.fold ? 1 : ss.nch));     //     t_j ; T_v = sum over segment v
             for (int a = 0; a < fr.n; ++a) v.p[a] = fr.t[a];
@@ -822,6 +832,7 @@ static int enqueue_forces_eval(bioen_hip_ctx* c, const ForcesRound& fr, const Ro
             launch_fwd_rows_forces_grad_share(c, fr.n, 0, &fr, false);      //     ... - (ybar_i - c_i) T_v, per segment
             if ((rc = exchange(c, X_YBAR, (size_t)c->mp * fr.n))) return rc;
             launch_forces_grad_sum_ranks(c, fr.n);                          //     added in segment order
+            if (c->affine) launch_forces_affine_grad(c, fr.n);
         }
         return 0;
     }
@@ -837,11 +848,13 @@ static int enqueue_forces_eval(bioen_hip_ctx* c, const ForcesRound& fr, const Ro
     if (with_grad) {
         MVec8 out{};
         for (int a = 0; a < fr.n; ++a) out.p[a] = fr.a[a];
+        if (c->affine) launch_forces_affine_const(c, fr, nullptr, false);   // S_OR: k_forces_t adds it to b
         launch_adj(c, fr.n, c->r_c, out, false);   // F3: b = yTilde^T r          [matrix pass 3]
         launch_forces_t(c, fr);               //     t_j
         for (int a = 0; a < fr.n; ++a) v.p[a] = fr.t[a];
         launch_fwd_partial(c, fr.n, v, true); //     gm_i = sum_j (yTilde_ij - ybar_i) t_j  [matrix pass 4]
         launch_fwd_rows_forces_grad(c, fr.n, c->fwd_ctiles);
+        if (c->affine) launch_forces_affine_grad(c, fr.n);
     }
     return 0;
 }
@@ -1414,7 +1427,9 @@ static int forces_guard(const bioen_hip_ctx* c, bool strip_path_ok = true) {
     // sharded contexts run the forces method in canonical segments only (not on the r01 streaming kernels)
     if (c->world != 1 && !(strip_path_ok && forces_canonical(c)))
         return fail(BIOEN_HIP_ESTATE, "not available on this structure-sharded context");
-    if (is_affine(c)) return fail(BIOEN_HIP_ESTATE, "the affine observable model is implemented for the log-weights method");
+    if (is_affine(c) && c->storage)          // the experiment's copies are pre-centred and its passes carry no offset
+        return fail(BIOEN_HIP_ESTATE, "the affine observable model is not served on the reduced-storage experiment's copies "
+                                      "(bioen_hip_ctx_set_storage(0), or remove the model)");
     if (c->storage && !(strip_path_ok && forces_fused_blocks(c) > 0))
         return fail(BIOEN_HIP_ESTATE, "the reduced-storage experiment serves the strip passes (M <= 1024) only");
     return 0;

@@ -67,6 +67,7 @@ enum ScalarSlot : int {
                                    //           every segment shifts its exponentials by its own maximum)
     S_B0 = S_INV + kMaxSeg,        // sum_i center_i r_i   (strip passes with centred operands: the adjoint's constant)
     S_UY,                          // sum_i ybar_raw_i r_i
+    S_OR,                          // forces on an affine model: sum_i off_i r_i, the part of b_j the matrix passes do not form
     S_COUNT
 };
 static_assert(S_COUNT <= kScalStride, "scalar slots");

@@ -178,6 +178,10 @@ void launch_forces_scalars(bioen_hip_ctx* c, const ForcesRound& r);
 // canonical-segment forms of the row-panel path (M > 1024; any number of ranks)
 void launch_forces_seg_exp(bioen_hip_ctx* c, const ForcesRound& r);                 // e = w0 exp(x - m_v) -> w ; X_EXP shares (needs launch_max on x)
 void launch_forces_seg_t(bioen_hip_ctx* c, const ForcesRound& r, int seg_sets);     // t ; T_v -> share 0 of the segment's seg_sets P_KL shares
+// affine observable model (ctx->affine only; kernels_forces.hip): the three steps the forces evaluation takes on M-vectors
+void launch_forces_affine_operand(bioen_hip_ctx* c, int K);          // um <- f o row_scale, before the first column-sum pass
+void launch_forces_affine_const(bioen_hip_ctx* c, const ForcesRound& fr, const double* center, bool add_b0);   // scal[S_OR] = sum_i off_i r_i (after k_rows_combine; center: ybar_c holds the centred share; add_b0: S_B0 += it)
+void launch_forces_affine_grad(bioen_hip_ctx* c, int K);             // gm <- gm o row_scale, after the segments' shares are added
 
 // ---- assembly of yTilde = sim / sigma on the device ----------------------------------------
 void launch_rows_div(bioen_hip_ctx* c, const double* sigma);          // Y[i][:] /= sigma_i (device pointer)

@@ -59,17 +59,22 @@ __global__ __launch_bounds__(kBlock) void k_forces_norm(ForcesRound r, const dou
 }
 
 // t_j = (theta (1 + log w_j - log w0_j) + b_j) w_j     (c_bioen_kernels_forces.c:320-328)
-__global__ __launch_bounds__(kBlock) void k_forces_t(ForcesRound r, const double* __restrict__ w0, int n) {
+// affine: the matrix pass has left sum_i (r s)_i Y_ij in b; the offsets' part of b_j, scal[S_OR] = sum_i off_i r_i
+// (k_forces_offset_const), is added here.  The plain model takes no such step: its bits stay.
+__global__ __launch_bounds__(kBlock) void k_forces_t(ForcesRound r, const double* __restrict__ w0, int n, bool affine) {
     const int a = blockIdx.y;
     const double* __restrict__ w = r.w[a];
     const double* __restrict__ b = r.a[a];
     double* __restrict__ t = r.t[a];
     const double theta = r.theta[a];
+    const double bconst = affine ? r.scal[a][S_OR] : 0.0;
     for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
         const double wv = w[j], w0v = w0[j];
         double dd = 1.0;
         if (wv >= DBL_MIN && w0v >= DBL_MIN) dd += log(wv) - log(w0v);
-        t[j] = (dd * theta + b[j]) * wv;
+        double bv = b[j];
+        if (affine) bv += bconst;
+        t[j] = (dd * theta + bv) * wv;
     }
 }
 
@@ -128,17 +133,24 @@ __global__ __launch_bounds__(kBlock) void k_forces_seg_exp(ForcesRound r, const 
 // k_forces_t on the NORMALISED weights (k_scale_w has run), with the block's share of T = sum_j t_j into a one-array stage: the
 // last matrix pass forms sum_j (Y_ij - c_i) t_j on the centred copy and the gradient takes (ybar_i - c_i) T off, as the
 // two-pass strip kernels do
-__global__ __launch_bounds__(kBlock) void k_forces_seg_t(ForcesRound r, const double* __restrict__ w0, int n, Xch xo) {
+// affine: + scal[S_OR] on b, as in k_forces_t (pass 3 runs on the uncentred operand: no other constant)
+__global__ __launch_bounds__(kBlock) void k_forces_seg_t(ForcesRound r, const double* __restrict__ w0, int n, Xch xo, bool affine) {
     __shared__ double sh[kWaves];
     const int a = blockIdx.y;
     const double* __restrict__ w = r.w[a];
     const double* __restrict__ b = r.a[a];
     double* __restrict__ t = r.t[a];
     const double theta = r.theta[a];
+    const double bconst = affine ? r.scal[a][S_OR] : 0.0;
     double s = 0.0;
     const SegPos sp = seg_pos(xo.npl, xo.segcols, n);
     for (int j = seg_first(sp); j < sp.jend; j += seg_step(xo.npl)) {
-        const d2 wv = ld_vec(w + j), w0v = ld_vec(w0 + j), bv = ld_vec(b + j);
+        const d2 wv = ld_vec(w + j), w0v = ld_vec(w0 + j);
+        d2 bv = ld_vec(b + j);
+        if (affine) {
+            bv.x += bconst;
+            bv.y += bconst;
+        }
         double d0 = 1.0, d1 = 1.0;
         if (wv.x >= DBL_MIN && w0v.x >= DBL_MIN) d0 += log(wv.x) - log(w0v.x);
         if (wv.y >= DBL_MIN && w0v.y >= DBL_MIN) d1 += log(wv.y) - log(w0v.y);
@@ -169,7 +181,7 @@ void launch_forces_seg_exp(bioen_hip_ctx* c, const ForcesRound& r) {
 
 void launch_forces_seg_t(bioen_hip_ctx* c, const ForcesRound& r, int seg_sets) {
     const Xch xo = make_xch(c, X_MAX, r.n * vec_grid(c));       // the block maxima have been consumed by k_forces_seg_exp
-    hipLaunchKernelGGL(k_forces_seg_t, dim3(vec_blocks(c), r.n), dim3(kBlock), 0, c->stream, r, c->fixed, c->n, xo);
+    hipLaunchKernelGGL(k_forces_seg_t, dim3(vec_blocks(c), r.n), dim3(kBlock), 0, c->stream, r, c->fixed, c->n, xo, c->affine);
     hipLaunchKernelGGL(k_forces_seg_tsum, dim3(r.n, c->vr), dim3(kBlock), 0, c->stream, xo, r, seg_sets);
 }
 
@@ -189,7 +201,7 @@ void launch_forces_norm(bioen_hip_ctx* c, const ForcesRound& r) {
 }
 
 void launch_forces_t(bioen_hip_ctx* c, const ForcesRound& r) {
-    hipLaunchKernelGGL(k_forces_t, dim3(vec_blocks(c), r.n), dim3(kBlock), 0, c->stream, r, c->fixed, c->n);
+    hipLaunchKernelGGL(k_forces_t, dim3(vec_blocks(c), r.n), dim3(kBlock), 0, c->stream, r, c->fixed, c->n, c->affine);
 }
 
 void launch_forces_scalars(bioen_hip_ctx* c, const ForcesRound& r) {
@@ -274,6 +286,55 @@ void launch_forces_blockmerge(bioen_hip_ctx* c, const ForcesRound& fr, int seg_s
 
 void launch_forces_w_from_x(bioen_hip_ctx* c, const ForcesRound& fr) {
     hipLaunchKernelGGL(k_forces_w_from_x, dim3(vec_blocks(c), fr.n), dim3(kBlock), 0, c->stream, fr, c->fixed, c->n);
+}
+
+// ---- affine observable model (ctx.hpp): the forces method's steps on M-vectors -------------------------------------------
+// With A_ij = off_i + sc_i Y_ij the evaluation is the plain one on the resident matrix with
+//   the operand of the first column-sum pass  f o sc                      (k_rows_scale on um),
+//   the constant of b_j  larger by  sum_i off_i r_i                       (k_forces_offset_const),
+//   the gradient  sc_i [ sum_j Y'_ij t_j - (ybar_raw_i - c_i) T ]         (k_rows_scale on gm, after the segments are added),
+// k_rows_combine having left r o sc in r_c already.  None of the three is launched on the plain model.
+__global__ __launch_bounds__(kBlock) void k_rows_scale(double* __restrict__ v, const double* __restrict__ row_scale, int count, int K) {
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock) v[i] *= row_scale[i / K];
+}
+
+// scal[S_OR] = sum_i off_i r_i, r as k_rows_combine's finish_row forms it from what it left in ybar_c (center: the
+// centred share, the centre goes back first); one block per problem, the rows in the order of that kernel's sums.
+// add_b0 (the two-pass strip path, whose pass 2 takes its constant from S_B0): S_B0 += the sum.
+__global__ __launch_bounds__(kBlock) void k_forces_offset_const(ForcesRound fr, int m, const double* __restrict__ ybar_c,
+                                                                const double* __restrict__ center, const double* __restrict__ YT,
+                                                                const double* __restrict__ row_offset,
+                                                                const double* __restrict__ row_scale, bool add_b0) {
+    __shared__ double sh[kWaves];
+    const int a = blockIdx.x, K = fr.n;
+    double s = 0.0;
+    for (int row = threadIdx.x; row < m; row += kBlock) {
+        double raw = ybar_c[(size_t)row * K + a];
+        if (center) raw += center[row];
+        const double res = fma(row_scale[row], raw, row_offset[row]) - YT[row];
+        s = fma(row_offset[row], res, s);
+    }
+    s = block_sum(s, sh);
+    if (threadIdx.x == 0) {
+        double* sc = fr.scal[a];
+        sc[S_OR] = s;
+        if (add_b0) sc[S_B0] += s;
+    }
+}
+
+void launch_forces_affine_operand(bioen_hip_ctx* c, int K) {
+    const int count = c->mp * K;
+    hipLaunchKernelGGL(k_rows_scale, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->um, c->row_scale, count, K);
+}
+
+void launch_forces_affine_const(bioen_hip_ctx* c, const ForcesRound& fr, const double* center, bool add_b0) {
+    hipLaunchKernelGGL(k_forces_offset_const, dim3(fr.n), dim3(kBlock), 0, c->stream, fr, c->m, c->ybar_c, center, c->YT,
+                       c->row_offset, c->row_scale, add_b0);
+}
+
+void launch_forces_affine_grad(bioen_hip_ctx* c, int K) {
+    const int count = c->mp * K;
+    hipLaunchKernelGGL(k_rows_scale, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->gm, c->row_scale, count, K);
 }
 
 // ---- the round's results to the host without a copy engine and without a stream synchronisation (r03) -------------

@@ -13,6 +13,8 @@ Both parameters enter affinely: yTilde(m) = 1/sigma + m (F-1)/sigma, yTilde(c) =
 m- (c-) independent matrix resident in HBM, step 2 needs one GEMV (yraw = Y . w, on the device) and a
 closed-form 1-D least-squares solution per group of rows, and step 1 sees the new parameter through
 ``Context.set_affine`` -- nothing is rebuilt or re-uploaded.
+
+``series`` runs the loop for the log-weights method, ``series_forces`` for the forces method.
 """
 import numpy as np
 
@@ -70,4 +72,46 @@ def series(ctx, thetas, G, g_init, lbfgs_params, YTilde, groups=None, row_offset
         out.append({"theta": float(theta), "w": w, "g": g, "fmin": info.fmin, "chi2": info.chi2, "S": -info.kl,
                     "scales": list(scales), "trace": trace})
     ctx.set_affine(None, None)
+    return out
+
+
+def series_forces(ctx, thetas, w0, forces_init, lbfgs_params, YTilde, groups=None, row_offset=None, scale0=1.0,
+                  iterations=10, verbose=False, accept_codes=(0, 1, 2)):
+    """The same theta-series for the forces method (the ``forces`` branch of ``procedure.py:62-83``).
+
+    ctx, groups, row_offset, accept_codes : as in ``series``
+    w0          : reference weights (the reference passes the same vector as start weights, ``procedure.py:71-74``)
+    forces_init : start forces of the FIRST optimisation only: every later one starts from the optimum of the
+                  one before it, across iterations AND thetas (``procedure.py:77``), and so do the scales
+    The model is removed from the context at the end, also when an optimisation raises.
+    Returns a list of dicts per theta: theta, w, forces, fmin, chi2, S, scales, trace (per iteration)."""
+    m = ctx.m
+    if groups is None:
+        groups = [np.arange(m)]
+    groups = [np.asarray(ix, dtype=np.int64) for ix in groups]
+    scales = [float(scale0)] * len(groups) if np.ndim(scale0) == 0 else [float(s) for s in scale0]
+    forces = np.array(forces_init, dtype=np.float64).ravel()
+    last = int(iterations) - 1
+    out = []
+    try:
+        for theta in thetas:
+            trace = []
+            for it in range(int(iterations)):
+                row_scale = np.ones(m)
+                for s, ix in zip(scales, groups):
+                    row_scale[ix] = s
+                ctx.set_affine(row_offset, row_scale)
+                # the refit needs Y . w only (last_average: 8 m bytes); the N weights travel once per theta
+                forces, w, info = ctx.opt_lbfgs_forces(forces, w0, float(theta), lbfgs_params, verbose=verbose,
+                                                       want_weights=(it == last))
+                if info.lbfgs_code not in accept_codes:
+                    raise RuntimeError("nuisance.series_forces, liblbfgs return code: %d" % info.lbfgs_code)
+                yraw, _ = ctx.last_average()
+                trace.append({"scales": list(scales), "fmin": info.fmin, "chi2": info.chi2,
+                              "iterations": info.iterations, "evaluations": info.evaluations})
+                scales = refit_scales(yraw, YTilde, row_offset, groups)
+            out.append({"theta": float(theta), "w": w, "forces": np.array(forces), "fmin": info.fmin, "chi2": info.chi2,
+                        "S": -info.kl, "scales": list(scales), "trace": trace})
+    finally:
+        ctx.set_affine(None, None)
     return out

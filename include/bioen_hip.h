@@ -200,7 +200,11 @@ int bioen_hip_ctx_set_ytilde_target(bioen_hip_ctx* ctx, const double* YTilde);
  * (scaling c: yTilde = c I/sigma, :141) nuisance parameters enter, so the refit loop of
  * bioen/analyze/procedure.py:79-83 needs no rebuild / re-upload of yTilde (the reference rebuilds it
  * on the host, observables.py:110-143).  row_offset = NULL means 0, row_scale = NULL means 1 (both m
- * long; one value per DEER trace / data set, repeated over its rows).  Log-weights method;
+ * long; one value per DEER trace / data set, repeated over its rows).  Both methods: the log-weights
+ * evaluations and Hessian-vector products, and every forces entry (weights, fdf, fdf_batch, the L-BFGS and
+ * GSL optimizers, sharded contexts included) -- there the forces enter the first pass as f_i row_scale_i
+ * and the gradient leaves the device multiplied by row_scale_i; (0, 1) gives the plain model's bits.  Not
+ * served: the forces method on the reduced-storage experiment's copies (BIOEN_HIP_ESTATE).
  * chi_squared() returns the raw yTilde . w and the chi^2 of the affine model. */
 int bioen_hip_ctx_set_affine(bioen_hip_ctx* ctx, const double* row_offset, const double* row_scale);
 /* EXPERIMENT, opt-in, never the default and never part of a headline number ("keep FP64 as the graded path;

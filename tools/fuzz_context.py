@@ -1,6 +1,6 @@
 """Development aid (GPU box): randomised checks of the context's data paths -- assembly from raw observables (row-major and
 structure-major), read-back of arbitrary blocks before and after the strip copies replace the matrix, the affine model
-against an explicitly rebuilt matrix, a changed target -- against numpy.  SEEDS=n (default 40)."""
+against an explicitly rebuilt matrix (both methods), a changed target -- against numpy.  SEEDS=n (default 40)."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -41,18 +41,30 @@ def run(first, nseeds):
                 block_ok("after the evaluations")
                 # affine model: off + sc * y  against a context on the rebuilt matrix
                 off = rng.normal(0, 1, M); sc = rng.uniform(0.5, 2.0, M)
+                fv = 1e-3 * rng.standard_normal(M); w0 = rng.dirichlet(np.ones(N) * 2.0)
+                ff, fgrad = ctx.forces_fdf(fv, w0, 3.0)
                 ctx.set_affine(off, sc)
                 fa, ga = ctx.logw_fdf(g, G, 3.0)
+                ffa, fga = ctx.forces_fdf(fv, w0, 3.0)
                 ctx.set_affine(None, None)
                 f2, g2 = ctx.logw_fdf(g, G, 3.0)
                 if f2 != f or not np.array_equal(g2, grad):
                     bad.append("%s: the plain model does not return its bits after an affine model was removed" % tag)
+                ff2, fgrad2 = ctx.forces_fdf(fv, w0, 3.0)
+                if ff2 != ff or not np.array_equal(fgrad2, fgrad):
+                    bad.append("%s: forces: the plain model does not return its bits after an affine model was removed" % tag)
                 # a changed target
                 YT2 = YT + rng.normal(0, 0.5, M)
                 ctx.set_target(YT2)
                 ft, gt = ctx.logw_fdf(g, G, 3.0)
-            with bioen_amd.Context(off[:, None] + sc[:, None] * y, YT) as cb:
+            eff = off[:, None] + sc[:, None] * y
+            with bioen_amd.Context(eff, YT) as cb:
                 fb, gb = cb.logw_fdf(g, G, 3.0)
+                ffb, fgb = cb.forces_fdf(fv, w0, 3.0)
+            # (the forces gradient is a difference of O(|yTilde| |t|) terms: absolute scale, as in tests/test_hip_parity.py)
+            if not (abs(ffa - ffb) <= 1e-11 * abs(ffb) and
+                    np.abs(fga - fgb).max() <= 1e-9 * np.abs(fgb).max() + 1e-13 * np.abs(eff).max() * (abs(ffb) + 1)):
+                bad.append("%s: forces: affine model vs rebuilt matrix: f %.3g grad %.3g" % (tag, abs(ffa - ffb) / abs(ffb), np.abs(fga - fgb).max() / max(np.abs(fgb).max(), 1e-300)))
             if not (abs(fa - fb) <= 1e-11 * abs(fb) and np.abs(ga - gb).max() <= 1e-9 * max(np.abs(gb).max(), 1e-2 * abs(fb))):
                 bad.append("%s: affine model vs rebuilt matrix: f %.3g grad %.3g" % (tag, abs(fa - fb) / abs(fb), np.abs(ga - gb).max() / max(np.abs(gb).max(), 1e-300)))
             with bioen_amd.Context(y, YT2) as cc:

@@ -1,6 +1,7 @@
 """Forces strip passes at BASELINE config 5 size (N = 1e6 x M = 512 by default): per-launch time of the two
 matrix passes at batch widths K = 1..8 through bioen_hip_forces_fdf_batch, and agreement of f / grad between
-batch widths.  (An A/B against an earlier tree: build that tree beside this one and run its copy of this file.)"""
+batch widths.  (An A/B against an earlier tree: build that tree beside this one and run its copy of this file, or point
+BIOEN_HIP_LIBRARY at its library.)  AFFINE=1: the same calls with an affine observable model set (Context.set_affine)."""
 import sys, os, time, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -15,8 +16,11 @@ YTilde = rng.normal(YTrue, sig_exp) / sig_exp
 w0 = np.full(N, 1.0 / N)
 thetas = np.logspace(3, -0.5, 8)
 forces = 1e-3 * rng.standard_normal((8, M))
-out = {"N": N, "M": M, "old": os.environ.get("BIOEN_HIP_STRIP_OLD", "0"), "K": {}}
+affine = os.environ.get("AFFINE", "0") == "1"
+out = {"N": N, "M": M, "old": os.environ.get("BIOEN_HIP_STRIP_OLD", "0"), "affine": int(affine), "K": {}}
 with bioen_amd.Context.synthetic(M, N, YTrue, sig_sim, sig_exp, YTilde, seed=12345) as ctx:
+    if affine:
+        ctx.set_affine(rng.normal(0.0, 1.0, M), rng.uniform(0.5, 2.0, M))
     f1, g1 = ctx.forces_fdf_batch(forces[:1], w0, thetas[:1])          # builds the strip copy, warms up
     ref = [ctx.forces_fdf_batch(forces[k:k + 1], w0, thetas[k:k + 1]) for k in range(8)]
     for K in [int(k) for k in os.environ.get("KS", "1,2,4,6,8").split(",")]:
