@@ -138,11 +138,21 @@ _SIGNATURES = {
     "bioen_hip_bfgs_logw_read_vec": (C.c_int, [ctx_p, C.c_int, dp]),
 }
 
+# every symbol include/bioen_hip_forces_hessp.h declares (the second public header: second-order information of the
+# forces method); bound by lib() beside the first table
+_SIGNATURES_FORCES_HESSP = {
+    "bioen_hip_forces_hessp": (C.c_int, [ctx_p, dp, dp, C.c_double, C.c_int, dp, dp, dp, dp]),
+}
+
 _lib = None
 
 
 def exported_symbols():
     return sorted(_SIGNATURES)
+
+
+def exported_symbols_forces_hessp():
+    return sorted(_SIGNATURES_FORCES_HESSP)
 
 
 def lib():
@@ -155,10 +165,11 @@ def lib():
                 "(or `python -c 'import __graft_entry__ as e; e.build()'`). "
                 "There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(L, name)          # AttributeError here = header/library mismatch
-            fn.restype = res
-            fn.argtypes = args
+        for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP):
+            for name, (res, args) in table.items():
+                fn = getattr(L, name)          # AttributeError here = header/library mismatch
+                fn.restype = res
+                fn.argtypes = args
         _lib = L
     return _lib
 
@@ -686,6 +697,62 @@ class Context(object):
                                          ptr(grad) if need_grad else None))
         return (f.value if need_f else None), grad
 
+    def forces_hessp(self, v, forces=None, w0=None, theta=None):
+        """Hessian-vector products H(forces) v of the forces objective (of the affine model if one is set) for up to 8
+        directions in one call: `v` is (m,) or (k, m), the result has its shape.  With `forces` (and w0, theta) the point
+        is evaluated first, as by forces_fdf -- f and grad are its bits --, and kept on the context: -> (hv, f, grad); `v`
+        None then only sets the point: -> (None, f, grad).  Without `forces` the product refers to the point the last such
+        call left (two fused matrix passes, whatever k): -> hv; BioenHipError (invalid state) once any other evaluation,
+        optimizer or change of the matrix state has run, or when the context's point is a log-weights point."""
+        fn = lib().bioen_hip_forces_hessp
+        if v is None:
+            if forces is None or w0 is None or theta is None:
+                raise ValueError("forces_hessp without v sets the point: it needs forces, w0 and theta")
+            fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
+            f = C.c_double(0.0)
+            grad = np.empty(self.m)
+            check(fn(self._h, ptr(fo), ptr(w0), float(theta), 0, None, None, C.byref(f), ptr(grad)))
+            return None, f.value, grad
+        va = as_f64(v)
+        if va.ndim not in (1, 2) or va.shape[-1] != self.m:
+            raise ValueError("v must be (M,) or (k, M) with M = %d, got %s" % (self.m, (va.shape,)))
+        k = 1 if va.ndim == 1 else va.shape[0]
+        if k < 1 or k > 8:
+            raise ValueError("forces_hessp takes 1 to 8 directions per call, got %d" % k)
+        hv = np.empty_like(va)
+        if forces is None:
+            check(fn(self._h, None, None, 0.0, k, ptr(va), ptr(hv), None, None))
+            return hv
+        if w0 is None or theta is None:
+            raise ValueError("forces_hessp with forces needs w0 and theta")
+        fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
+        f = C.c_double(0.0)
+        grad = np.empty(self.m)
+        check(fn(self._h, ptr(fo), ptr(w0), float(theta), k, ptr(va), ptr(hv), C.byref(f), ptr(grad)))
+        return hv, f.value, grad
+
+    def forces_hessian(self, forces=None, w0=None, theta=None):
+        """The dense Hessian (m, m) of the forces objective: ceil(m / 8) forces_hessp calls with unit directions.  With
+        `forces` the point is set first: -> (H, f, grad); without, at the kept point: -> H.  The result is symmetrised as
+        (H + H^T) / 2: the products' own asymmetry -- the two matrix passes of a product add in different orders for a
+        row and for a column -- is rounding, checked here to be at most 1e-10 of the largest entry (measured: see DESIGN 6d)."""
+        out = None
+        if forces is not None:
+            _, f, grad = self.forces_hessp(None, forces=forces, w0=w0, theta=theta)
+            out = (f, grad)
+        m = self.m
+        H = np.empty((m, m))
+        eye = np.eye(m)
+        for i0 in range(0, m, 8):
+            H[i0:i0 + 8] = self.forces_hessp(eye[i0:i0 + 8])
+        scale = np.abs(H).max()
+        asym = np.abs(H - H.T).max()
+        if not asym <= 1e-10 * scale:
+            raise BioenHipError("forces_hessian: the products are not symmetric: max |H - H^T| = %.3g, max |H| = %.3g"
+                                % (asym, scale))
+        H = 0.5 * (H + H.T)
+        return H if out is None else (H, out[0], out[1])
+
     def forces_fdf_batch(self, forces, w0, thetas, need_grad=True):
         """K <= 8 evaluations sharing every matrix pass.  forces: (K, m), thetas: (K,) -> (f[K], grad[K, m] or None).
         Every column is the single call's result bit for bit, with or without an affine model."""
@@ -778,7 +845,7 @@ class Context(object):
     def kernel_stats(self):
         out = {}
         for which, name in ((0, "forward"), (1, "adjoint"), (2, "hessp_dots"), (3, "hessp_tangent"), (4, "hessp_combine"),
-                            (5, "hessp_epilogue")):
+                            (5, "hessp_epilogue"), (6, "forces_hessp_tangent"), (7, "forces_hessp_product")):
             ms = C.c_double(0.0)
             cnt = C.c_longlong(0)
             pp = C.c_longlong(0)

@@ -19,6 +19,7 @@
 #include <thread>
 
 #include "ctx.hpp"
+#include "../../include/bioen_hip_forces_hessp.h"
 #include "kernels.hpp"
 #include "lbfgs.hpp"
 #include "multimin.hpp"
@@ -2179,3 +2180,4 @@ static void comm_release(bioen_hip_ctx* c) {
 #include "api_multimin.inl"
 #include "api_bfgs.inl"
 #include "api_hessp.inl"
+#include "api_forces_hessp.inl"

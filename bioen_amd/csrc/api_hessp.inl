@@ -19,7 +19,7 @@ static int hessp_buffers(bioen_hip_ctx* c, int k) {
 }
 
 static void hessp_free(bioen_hip_ctx* c) {
-    double* bufs[] = {c->point_ybar, c->point_fac, c->hp_scal};
+    double* bufs[] = {c->point_ybar, c->point_fac, c->hp_scal, c->fpoint_ybar, c->fpoint_rs, c->fpoint_q};
     for (double* b : bufs)
         if (b) (void)hipFree(b);
     for (double*& b : c->hp_vec) {
@@ -27,6 +27,7 @@ static void hessp_free(bioen_hip_ctx* c) {
         b = nullptr;
     }
     c->point_ybar = c->point_fac = c->hp_scal = nullptr;
+    c->fpoint_ybar = c->fpoint_rs = c->fpoint_q = nullptr;
     c->point_valid = 0;
 }
 
@@ -94,6 +95,9 @@ extern "C" int bioen_hip_logw_hessp(bioen_hip_ctx* c, const double* g, const dou
     if (k < 0 || k > kMaxBatch) return fail(BIOEN_HIP_EINVAL, "k must be in [0, 8]");
     if (k > 0 && (!v || !hv)) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (g && !G) return fail(BIOEN_HIP_EINVAL, "g without G");
+    if (!g && c->point_valid && c->point_kind != 0)      // ONE point per context, of either method
+        return fail(BIOEN_HIP_ESTATE, "the point on this context is a forces point (set by bioen_hip_forces_hessp): "
+                                      "call bioen_hip_logw_hessp with g first");
     if (!g && !c->point_valid) {
         const std::string m = c->point_lost
                                   ? std::string("the point of the last bioen_hip_logw_hessp call with g is gone: dropped by ") + c->point_lost
@@ -113,6 +117,7 @@ extern "C" int bioen_hip_logw_hessp(bioen_hip_ctx* c, const double* g, const dou
         // bioen_hip_logw_fdf's evaluation, launch for launch
         if ((rc = eval_logw_point(c, make_round(c, one, 1, nullptr, &theta), true, true, f, grad))) return rc;
         c->point_theta = theta;
+        c->point_kind = 0;
         c->point_valid = 1;
         c->point_lost = nullptr;
     }

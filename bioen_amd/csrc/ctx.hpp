@@ -119,7 +119,8 @@ struct Xch {              // one stage, as the kernels see it
 
 struct BfgsSession;   // dense inverse-Hessian BFGS session (api_bfgs.inl)
 
-constexpr int kTimerKinds = 6;     // 0 / 1: forward / adjoint matrix pass; 2..5: the Hessian-vector product's dots, tangent, combine, epilogue
+constexpr int kTimerKinds = 8;     // 0 / 1: forward / adjoint matrix pass; 2..5: the Hessian-vector product's dots, tangent, combine, epilogue;
+                                   // 6 / 7: the two fused passes of the forces method's product (M <= 1024)
 struct KernelTimer {
     bool enabled = false;
     double total_ms[kTimerKinds] = {};
@@ -285,11 +286,16 @@ struct bioen_hip_ctx {
     // segment's softmax factor (S_INV covers the local segments only) and the directions' work vectors.  Dropped by every
     // call that evaluates anything or changes the matrix state (point_drop).
     int point_valid = 0;
+    int point_kind = 0;                  // 0: a log-weights point, 1: a forces point (bioen_hip_forces_hessp) -- ONE point per context
     const char* point_lost = nullptr;    // what dropped it (for the message)
     double point_theta = 0.0;
     double* point_ybar = nullptr;        // mp: raw ybar of the point
     double* point_fac = nullptr;         // nseg: e^{m_v - M} / S of the point
     double* hp_scal = nullptr;           // kMaxBatch x kScalStride: the directions' scalars (S_B0, S_UY, vbar, v.grad)
+    // a forces point (api_forces_hessp.inl): slot 0 holds x' and the scalars, c->fixed w0; beyond the slot:
+    double* fpoint_ybar = nullptr;       // mp: ybar' = ybar - strip_center of the point
+    double* fpoint_rs = nullptr;         // mp: r o s
+    double* fpoint_q = nullptr;          // ld: q_j - qbar
     double* hp_vec[2 * bioen::kMaxBatch] = {};   // per direction: v | t, then the centred adjoint c, then H v (ld doubles each,
                                                  // allocated at a direction's first use, kept until the context is destroyed)
 

@@ -160,6 +160,32 @@ void launch_hessp_tangent(bioen_hip_ctx* c, const HesspArgs& h);       // finish
 void launch_hessp_combine(bioen_hip_ctx* c, const HesspArgs& h, const double* center);   // shares -> r_c, ybar_c, S_B0, S_UY
 void launch_hessp_epilogue(bioen_hip_ctx* c, const HesspArgs& h);
 
+// ---- Hessian-vector products of the forces objective (kernels_forces_hessp.hip; the passes: strip_plan.cpp) ----------
+void launch_fhp_keep(bioen_hip_ctx* c, double* ybar, double* rs);      // after a K = 1 evaluation: ybar_c -> ybar', r_c -> r o s
+void launch_fhp_point_q(bioen_hip_ctx* c, const double* ybar, const double* rs, const double* pscal, double theta,
+                        const double* x, double* qv);                  // qv: b' in, q - qbar out
+// center: NULL on the fused passes (column sums on Y'), the strip centre on the row panels (column sums on Y)
+void launch_fhp_prepare(bioen_hip_ctx* c, int K, const double* ybar, const double* pscal, double* hscal, const double* center);   // ybar_c, S_LOGS, dxbar
+void launch_fhp_combine(bioen_hip_ctx* c, int K, const double* ybar, double* hscal, const double* center);   // gm = dy' -> r_c = pass 2's operand, S_B0 = -cbar
+struct FhpVecArgs {                 // the N-vector kernels of the row-panel path (blockIdx.y = direction a)
+    int n;
+    const double* w;                // the point: normalised weights, the prior, b = Y^T (r o s), its scalar slot
+    const double* w0;
+    const double* b;
+    const double* pscal;
+    double* q;                      // the point's q - qbar
+    const double* dx[kMaxBatch];    // per direction: dx | the work vector (w dx, then c, then s) | scalars | partials
+    double* t[kMaxBatch];
+    const double* scal[kMaxBatch];
+    double* part[kMaxBatch];
+    double theta;
+};
+void launch_fhp_seg_point_q(bioen_hip_ctx* c, const FhpVecArgs& h);
+void launch_fhp_seg_t(bioen_hip_ctx* c, const FhpVecArgs& h, bool product, int seg_sets);   // t | s, T_v -> share 0 of the segment's P_KL shares
+void launch_forces_hp_tangent(bioen_hip_ctx* c, const struct ForcesRound& fr);         // [matrix pass 1 of a product]
+void launch_forces_hp_product(bioen_hip_ctx* c, const struct ForcesRound& fr);         // [matrix pass 2]
+void launch_forces_colsum(bioen_hip_ctx* c, const double* u_c, double* out);           // out = Y'^T u on the forces passes' copy
+
 // ---- forces N-vector kernels (blockIdx.y = batch position) ---------------------------------
 struct ForcesRound {
     int n;

@@ -16,8 +16,10 @@ namespace bioen {
 #ifndef STRIP2_GB2
 #define STRIP2_GB2 2
 #endif
-template <int K, bool NT, bool XY, int STORE = 0, bool ADJ = false>        // ADJ: as in k_strip
+template <int K, bool NT, int MODE, int STORE = 0, bool ADJ = false>        // MODE, ADJ: as in k_strip
 __global__ __launch_bounds__(512, 2) void k_strip2(StripArgs q, ForcesRound fr) {
+    constexpr bool XY = MODE == SM_XY;
+    constexpr bool HP = MODE == SM_TANGENT || MODE == SM_PRODUCT;
     constexpr int RH = 2;                           // 64-row halves per wave
     constexpr int WR = 64 * RH;                     // rows per wave
     constexpr int NK = (K + 3) / 4;                 // problem quads
@@ -44,7 +46,7 @@ __global__ __launch_bounds__(512, 2) void k_strip2(StripArgs q, ForcesRound fr) 
     }
     for (int i = t; i < 128; i += blockDim.x) tv[i] = 0.0;         // problems k >= K of a quad stay zero
     for (int i = t; i < lrows; i += blockDim.x) cl[i] = i < q.mp ? q.center[i] : 0.0;
-    if (t < 8) scale[t] = 1.0;
+    if (!HP && t < 8) scale[t] = 1.0;
 
     // P3 accumulators: row block h (16 rows), problem quad kq: lane 16 i + 4 blk + j holds
     // row rbase + 16 h + 4 blk + i, problem 4 kq + j
@@ -69,15 +71,35 @@ __global__ __launch_bounds__(512, 2) void k_strip2(StripArgs q, ForcesRound fr) 
 #pragma unroll
     for (int k = 1; k < K; ++k)
         if (pk == k) {
-            ak = fr.a[k];
+            if constexpr (!HP) ak = fr.a[k];        // (the product's forms: every direction reads the point's x, theta, S_LOGS)
             sck = fr.scal[k];
             pak = fr.part[k];
-            thk = fr.theta[k];
+            if constexpr (!HP) thk = fr.theta[k];
         }
-    if (!XY && p2) {
+    if constexpr (HP) {
+        logs = fr.scal[0][S_LOGS];
+        theta = thk;
+    } else if (!XY && p2) {
         logs = sck[S_LOGS];
         b0 = sck[S_B0];
         theta = thk;
+    }
+    // The product's forms (k_strip has the arguments' meaning).  This kernel has no register to spare beside a3 and the
+    // prefetch: what is the same for every direction stays wave-uniform (above), and the direction's two constants of
+    // SM_PRODUCT, dxbar and -cbar, wait in `scale`, which only the XY form uses otherwise.
+    // ... and the direction's dx vector is chosen among the kernel arguments where it is used, not held across the strips.
+    auto dx_of = [&]() {
+        double* p = fr.w[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k)
+            if (pk == k) p = fr.w[k];
+        return p;
+    };
+    if constexpr (HP) {
+        if (MODE == SM_PRODUCT && p2 && pc == 0) {
+            scale[2 * pk] = sck[S_SPARE0];
+            scale[2 * pk + 1] = sck[S_B0];
+        }
     }
     double shift = 0.0;                             // ADJ: k_strip_adj's constant (k_strip)
     if constexpr (ADJ) {                            // (accumulate: 0 = start at the shift, 1 = continue the panels before, 2 = start at 0)
@@ -198,10 +220,18 @@ __global__ __launch_bounds__(512, 2) void k_strip2(StripArgs q, ForcesRound fr) 
         // prefetch would wait for the whole strip after next
         const size_t col = (size_t)s * kStripCols + pc;
         double w0v = 0.0, xv = 0.0;
+        double dxv = 0.0, qv = 0.0;                 // PRODUCT: the direction's dx_j, the point's q_j - qbar
+        double* dxp = nullptr;                      // TANGENT: where dx_j goes (formed here: `col` need not outlive P1)
+        if constexpr (MODE == SM_TANGENT) dxp = dx_of() + col;
+        const bool validc = col < (size_t)q.n;
         if constexpr (!ADJ) {
             if (p2) {
                 w0v = q.w0[col];
                 if (!XY) xv = ak[col];
+                if constexpr (MODE == SM_PRODUCT) {
+                    dxv = dx_of()[col];
+                    qv = fr.t[0][col];
+                }
             }
         } else {
             if (p2 && q.accumulate == 1) xv = ak[col];            // the column sums of the row panels before this one
@@ -301,6 +331,20 @@ __global__ __launch_bounds__(512, 2) void k_strip2(StripArgs q, ForcesRound fr) 
                     if (pc == 0) scale[pk] = sc;
                     tv[pk * 16 + pc] = e;
                 }
+            } else if constexpr (HP) {                            // k_strip's forms of the same name
+                if (p2) {
+                    const bool valid = validc;
+                    const double wv = w0v * exp(xv - logs);
+                    double tval;
+                    if constexpr (MODE == SM_TANGENT) {
+                        __builtin_nontemporal_store(valid ? colsum : 0.0, dxp);
+                        tval = valid ? wv * colsum : 0.0;
+                    } else {
+                        tval = valid ? wv * fma(dxv - scale[2 * pk], qv + theta, colsum + scale[2 * pk + 1]) : 0.0;
+                    }
+                    tv[pk * 16 + pc] = tval;
+                    zacc += tval;
+                }
             } else if (p2) {
                 const double lrat = xv - logs;                    // log(w / w0)
                 const double wv = w0v * exp(lrat);
@@ -353,10 +397,10 @@ __global__ __launch_bounds__(512, 2) void k_strip2(StripArgs q, ForcesRound fr) 
     if constexpr (!ADJ) flush((vloc - 1) * q.gs + wk.g);           // the last segment's set
 }
 
-template <int K, bool NT, bool XY, int STORE, bool ADJ>
+template <int K, bool NT, int MODE, int STORE, bool ADJ>
 static void launch(bioen_hip_ctx* c, const StripArgs& q, const ForcesRound& fr, dim3 block, size_t lds) {
-    allow_big_lds<&k_strip2<K, NT, XY, STORE, ADJ>>(c);
-    BIOEN_LAUNCH_TIMED(c, (k_strip2<K, NT, XY, STORE, ADJ>), dim3(q.nblk), block, lds, q, fr);
+    allow_big_lds<&k_strip2<K, NT, MODE, STORE, ADJ>>(c);
+    BIOEN_LAUNCH_TIMED(c, (k_strip2<K, NT, MODE, STORE, ADJ>), dim3(q.nblk), block, lds, q, fr);
 }
 
 void run_k_strip2(bioen_hip_ctx* c, const StripArgs& q, const ForcesRound& fr, dim3 block, size_t lds, const StripForm& f) {
@@ -364,9 +408,11 @@ void run_k_strip2(bioen_hip_ctx* c, const StripArgs& q, const ForcesRound& fr, d
         for_value<1, 0>(f.nt, [&](auto nt) {
             constexpr int K = decltype(k)::value;
             constexpr bool NT = decltype(nt)::value != 0;
-            if (f.adj) return launch<K, NT, true, 0, true>(c, q, fr, block, lds);      // (FP64 copy only)
+            if (f.adj) return launch<K, NT, SM_XY, 0, true>(c, q, fr, block, lds);      // (FP64 copy only)
+            if (f.mode == SM_TANGENT) return launch<K, NT, SM_TANGENT, 0, false>(c, q, fr, block, lds);      // the product's forms: FP64 copy only
+            if (f.mode == SM_PRODUCT) return launch<K, NT, SM_PRODUCT, 0, false>(c, q, fr, block, lds);
             for_value<1, 0>(f.xy, [&](auto xy) {
-                constexpr bool XY = decltype(xy)::value != 0;
+                constexpr int XY = decltype(xy)::value != 0 ? SM_XY : SM_BT;
                 for_value<1, 2, 0>(f.store, [&](auto st) { launch<K, NT, XY, decltype(st)::value, false>(c, q, fr, block, lds); });
             });
         });

@@ -16,9 +16,14 @@ namespace bioen {
 // parity).  Same operands, same order of every sum: the bits of a problem do not depend on which form served it.
 // ADJ (r05): the column-sum half of pass 1 alone -- out_k[j] = sum_i Y'_ij u_ik + shift_k, the log-weights ADJOINT
 // (k_strip_adj's product) on the ROW-sum order copy: what lets the log-weights method run with ONE strip copy of the
-// matrix (ctx.hpp: one_copy).  No softmax, no row sums, no sets; instantiated with XY = true, DEPTH 2.
-template <int K, bool NT, bool XY, int DEPTH = STRIP_DEPTH, int STORE = 0, bool ADJ = false>
+// matrix (ctx.hpp: one_copy).  No softmax, no row sums, no sets; instantiated with MODE = SM_XY, DEPTH 2.
+// MODE (strip.hpp: StripMode): SM_BT / SM_XY the two passes of the evaluation; SM_TANGENT / SM_PRODUCT the two passes of a
+// Hessian-vector product at a kept point -- P2 forms of their own on the BT skeleton (no running maximum, no
+// rescale, the set's share of sum_j tv_j in P_KL); P1, P3, the fetch, the flush and the strip loop are shared.
+template <int K, bool NT, int MODE, int DEPTH = STRIP_DEPTH, int STORE = 0, bool ADJ = false>
 __global__ __launch_bounds__(512, STRIP_WAVES_PER_SIMD) void k_strip(StripArgs q, ForcesRound fr) {
+    constexpr bool XY = MODE == SM_XY;
+    constexpr bool HP = MODE == SM_TANGENT || MODE == SM_PRODUCT;
     constexpr int NK = (K + 3) / 4;                 // problem quads
     constexpr bool DEFER = DEPTH == 3;
     constexpr int SETS = DEPTH == 2 ? 2 : 1;        // register sets (strips in flight per wave)
@@ -84,6 +89,17 @@ __global__ __launch_bounds__(512, STRIP_WAVES_PER_SIMD) void k_strip(StripArgs q
         logs = sck[S_LOGS];
         b0 = sck[S_B0];
         theta = thk;
+    }
+    // the product's forms: fr.a = the point's x (every direction the same), fr.w[k] = the direction's dx (TANGENT: out,
+    // PRODUCT: in), fr.t = the point's q - qbar; the direction's scalars: S_LOGS (the point's), S_SPARE0 = dxbar, S_B0 = -cbar
+    double* dxk = nullptr;
+    double dxbar = 0.0;
+    if constexpr (HP) {
+        dxk = fr.w[0];
+#pragma unroll
+        for (int k = 1; k < K; ++k)
+            if (pk == k) dxk = fr.w[k];
+        if (MODE == SM_PRODUCT && p2) dxbar = sck[S_SPARE0];
     }
     double shift = 0.0;                             // ADJ: sum_i u_ik (center_i - ybar_ik), k_strip_adj's constant
     if constexpr (ADJ) {                            // (accumulate: 0 = start at the shift, 1 = continue the panels before, 2 = start at 0)
@@ -261,10 +277,15 @@ __global__ __launch_bounds__(512, STRIP_WAVES_PER_SIMD) void k_strip(StripArgs q
         // prefetch would wait for the whole strip after next
         const size_t col = (size_t)s * kStripCols + pc;
         double w0v = 0.0, xv = 0.0;
+        double dxv = 0.0, qv = 0.0;                 // PRODUCT: the direction's dx_j, the point's q_j - qbar
         if constexpr (!ADJ) {
             if (p2) {
                 w0v = q.w0[col];
                 if (!XY) xv = ak[col];
+                if constexpr (MODE == SM_PRODUCT) {
+                    dxv = dxk[col];
+                    qv = fr.t[0][col];
+                }
             }
         } else {
             if (p2 && q.accumulate == 1) xv = ak[col];            // the column sums of the row panels before this one
@@ -348,6 +369,20 @@ __global__ __launch_bounds__(512, STRIP_WAVES_PER_SIMD) void k_strip(StripArgs q
                     if (pc == 0) scp[pk] = sc;
                     tvp[pk * 16 + pc] = e;
                 }
+            } else if constexpr (HP) {
+                if (p2) {
+                    const bool valid = col < (size_t)q.n;
+                    const double wv = w0v * exp(xv - logs);       // the point's weight, as the BT form makes it
+                    double tval;
+                    if constexpr (MODE == SM_TANGENT) {           // dx_j out, tv = w_j dx_j
+                        __builtin_nontemporal_store(valid ? colsum : 0.0, dxk + col);
+                        tval = valid ? wv * colsum : 0.0;
+                    } else {                                      // tv = s_j = w_j [(dx_j - dxbar)(q_j - qbar + theta) + c_j - cbar]
+                        tval = valid ? wv * fma(dxv - dxbar, qv + theta, colsum + b0) : 0.0;
+                    }
+                    tvp[pk * 16 + pc] = tval;
+                    zacc += tval;
+                }
             } else if (p2) {
                 const double lrat = xv - logs;                    // log(w / w0)
                 const double wv = w0v * exp(lrat);
@@ -427,10 +462,10 @@ __global__ __launch_bounds__(512, STRIP_WAVES_PER_SIMD) void k_strip(StripArgs q
 #endif
 }
 
-template <int K, bool NT, bool XY, int DEPTH, int STORE, bool ADJ>
+template <int K, bool NT, int MODE, int DEPTH, int STORE, bool ADJ>
 static void launch(bioen_hip_ctx* c, const StripArgs& q, const ForcesRound& fr, dim3 block, size_t lds) {
-    allow_big_lds<&k_strip<K, NT, XY, DEPTH, STORE, ADJ>>(c);
-    BIOEN_LAUNCH_TIMED(c, (k_strip<K, NT, XY, DEPTH, STORE, ADJ>), dim3(q.nblk), block, lds, q, fr);
+    allow_big_lds<&k_strip<K, NT, MODE, DEPTH, STORE, ADJ>>(c);
+    BIOEN_LAUNCH_TIMED(c, (k_strip<K, NT, MODE, DEPTH, STORE, ADJ>), dim3(q.nblk), block, lds, q, fr);
 }
 
 // Instantiated: the ADJ form with two register sets on the FP64 copy; K <= 4: two register sets; K > 4: the deferred form
@@ -440,9 +475,12 @@ void run_k_strip(bioen_hip_ctx* c, const StripArgs& q, const ForcesRound& fr, di
         for_value<1, 0>(f.nt, [&](auto nt) {
             constexpr int K = decltype(k)::value;
             constexpr bool NT = decltype(nt)::value != 0;
-            if (f.adj) return launch<K, NT, true, 2, 0, true>(c, q, fr, block, lds);
+            if (f.adj) return launch<K, NT, SM_XY, 2, 0, true>(c, q, fr, block, lds);
+            // the product's forms: the FP64 copy, the width's default depth
+            if (f.mode == SM_TANGENT) return launch<K, NT, SM_TANGENT, (K > 4 ? 3 : 2), 0, false>(c, q, fr, block, lds);
+            if (f.mode == SM_PRODUCT) return launch<K, NT, SM_PRODUCT, (K > 4 ? 3 : 2), 0, false>(c, q, fr, block, lds);
             for_value<1, 0>(f.xy, [&](auto xy) {
-                constexpr bool XY = decltype(xy)::value != 0;
+                constexpr int XY = decltype(xy)::value != 0 ? SM_XY : SM_BT;
                 if constexpr (K > 4) {
                     if (!f.store && f.depth != 3)
                         return for_value<1, 2>(f.depth, [&](auto d) { launch<K, NT, XY, decltype(d)::value, 0, false>(c, q, fr, block, lds); });

@@ -288,11 +288,20 @@ inline int strip_ilv(const bioen_hip_ctx* c) { return std::max(1, c->strip_ilv);
 inline int reduced_rows(const bioen_hip_ctx* c) { return (int)round_up((size_t)c->m, c->mp > 512 ? 2 * kWaveRows : kWaveRows); }
 bool one_copy_by_default(const bioen_hip_ctx* c);      // strip_plan.cpp
 
+// P2 of the forces kernels (k_strip, k_strip2): what a strip's column sums become before the row-sum product takes them
+enum StripMode : int {
+    SM_BT = 0,          // pass 2 of the evaluation: b, t
+    SM_XY = 1,          // pass 1: x out, online softmax, e
+    SM_TANGENT = 2,     // pass 1 of a Hessian-vector product at a kept point: dx out, w dx
+    SM_PRODUCT = 3,     // pass 2 of it: s
+};
+
 // Which instantiation of its family a launch runs: all the template parameters ever decide.
 struct StripForm {
     int K;              // batch width 1 .. 8
     bool nt;            // nontemporal matrix loads
     bool xy;            // forces kernels: pass 1 (x, softmax, ybar) | pass 2 (b, t, Y' t)
+    int mode;           // forces kernels: SM_TANGENT / SM_PRODUCT, the product's forms (else 0: xy decides)
     bool adj;           // forces kernels: the column-sum half alone (the one-copy log-weights adjoint)
     int depth;          // k_strip: 2 = two register sets, 1 = one, 3 = one + deferred row sums (the default at K > 4)
     int store;          // 0 FP64 | 1, 2: the reduced-storage experiment's copies

@@ -213,12 +213,14 @@ void launch_adj_strip(bioen_hip_ctx* c, int K, const double* u_c, const MVec8& o
 // A forces pass (M <= 1024).  Strips in flight per wave of k_strip: two register sets, except at K > 4, where the second
 // one does not fit (pass 1: the compiler spilled): one set + the row-sum product deferred behind the next strip's barrier
 // (DEPTH 3, r04).  BIOEN_HIP_STRIP_DEPTH5=2 / 1: the r03 forms (A/B; FP64 copies only; read at every launch).
-static void forces_pass(bioen_hip_ctx* c, const ForcesRound& fr, bool xy, const double* u_c) {
+// mode: SM_TANGENT / SM_PRODUCT, the forms of a Hessian-vector product (FP64 copy, the width's default depth), else 0
+static void forces_pass(bioen_hip_ctx* c, const ForcesRound& fr, bool xy, const double* u_c, int mode = 0) {
     StripArgs q = forces_args(c, 0, fr.n, false, forces_sets(c).gs, u_c);
     q.stamps = reinterpret_cast<long long*>(c->strip_stamps);
     StripForm f = strip_form(c, fr.n);
     f.xy = xy;
-    const int depth5 = c->storage ? 3 : env_flag("BIOEN_HIP_STRIP_DEPTH5", 3);
+    f.mode = mode;
+    const int depth5 = (c->storage || mode) ? 3 : env_flag("BIOEN_HIP_STRIP_DEPTH5", 3);
     f.depth = fr.n <= 4 ? 2 : (depth5 == 1 || depth5 == 2) ? depth5 : 3;
     const bool tall = strip_tall(c->mp);
     const ForcesBlock b = forces_block(panel_mps(c, 0), c->mp, !tall && f.depth == 3);
@@ -239,6 +241,36 @@ void launch_forces_xy(bioen_hip_ctx* c, const ForcesRound& fr, int seg_sets) {
 void launch_forces_bt(bioen_hip_ctx* c, const ForcesRound& fr) {
     TimedLaunch tl(c, 0, fr.n);
     forces_pass(c, fr, false, c->r_c);
+}
+
+// ---- Hessian-vector products of the forces objective at a kept point (M <= 1024) ---------------------------
+// pass 1: dx = Y'^T (v o s) -> fr.w, w dx, Y' . (w dx); fr.a = the point's x, fr.scal = the directions' scalars
+void launch_forces_hp_tangent(bioen_hip_ctx* c, const ForcesRound& fr) {
+    TimedLaunch tl(c, 6, fr.n);
+    forces_pass(c, fr, false, c->um, SM_TANGENT);
+}
+
+// pass 2: c = Y'^T (dy' o s o s), s_j, Y' . s; fr.t = the point's q - qbar
+void launch_forces_hp_product(bioen_hip_ctx* c, const ForcesRound& fr) {
+    TimedLaunch tl(c, 7, fr.n);
+    forces_pass(c, fr, false, c->r_c, SM_PRODUCT);
+}
+
+// out_j = sum_i Y'_ij u_i on the forces passes' copy (one operand): the ADJ form of the forces kernels, from zero
+void launch_forces_colsum(bioen_hip_ctx* c, const double* u_c, double* out) {
+    TimedLaunch tl(c, 1, 1);
+    const int gs = std::max(1, std::min(strip_sps(c), 256 * forces_per_cu(c)));
+    StripArgs q = forces_args(c, 0, 1, false, gs, u_c);
+    q.accumulate = 2;
+    ForcesRound fr{};
+    fr.n = 1;
+    fr.a[0] = out;
+    fr.scal[0] = c->scal;           // (not read: the sum starts at zero)
+    StripForm f = strip_form(c, 1);
+    f.adj = true;
+    const ForcesBlock b = forces_block(q.mps, q.mp);
+    if (strip_tall(q.mp)) run_k_strip2(c, q, fr, dim3(b.threads), b.lds, f);
+    else run_k_strip(c, q, fr, dim3(b.threads), b.lds, f);
 }
 
 }  // namespace bioen

@@ -365,6 +365,26 @@ def grad_bioen_log_posterior_forces(forces, w0, yTilde, YTilde, theta, caching=F
     return grad
 
 
+def hessp_bioen_log_posterior_forces(forces, p, w0, yTilde, YTilde, theta, caching=False):
+    """H(forces) p on the device (not in the reference: c_bioen.pyx has first-order entries only); p (m,) or (k <= 8, m)"""
+    ctx, cached = _context_for(yTilde, YTilde)
+    try:
+        hv, _, _ = ctx.forces_hessp(p, forces=forces, w0=w0, theta=theta)
+    finally:
+        _release(ctx, cached)
+    return hv
+
+
+def hessian_bioen_log_posterior_forces(forces, w0, yTilde, YTilde, theta, caching=False):
+    """the dense Hessian (m, m) on the device: ceil(m / 8) batched products at one kept point"""
+    ctx, cached = _context_for(yTilde, YTilde)
+    try:
+        H, _, _ = ctx.forces_hessian(forces=forces, w0=w0, theta=theta)
+    finally:
+        _release(ctx, cached)
+    return H
+
+
 def bioen_opt_bfgs_forces(forces, w0, yTilde, YTilde, theta, params):
     """-> (forces_opt[m], fmin); c_bioen.pyx:620-716"""
     global last_opt_info

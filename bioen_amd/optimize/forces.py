@@ -13,6 +13,7 @@ from __future__ import print_function
 import time
 
 import numpy as np
+import scipy.optimize as sopt
 
 from . import common
 from .ext import c_bioen
@@ -115,21 +116,118 @@ def grad_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta, use_c=True)
     return (yT - ybar[:, None]).dot(t)        # centred, as forces.py:329-332 (no cancellation)
 
 
+# ------------------------------------------------------------------ second order
+def _hessp_base(forces, V, w0, yTilde, YTilde, theta):
+    """H V for the columns of V (m, k), centred throughout:
+
+      x = A^T f,  w ~ w0 e^x,  ybar = A w,  r = ybar - YTilde,  q = theta x + A^T r
+      dx  = A^T v - <A^T v>                        (<.> the average under w)
+      dy  = A (w dx)
+      s   = w [ dx (q - <q>) + theta dx + (A^T dy - <A^T dy>) ]
+      H v = (A - ybar) s
+
+    Constants added to x, q, dx or the bracket of s cancel in the centred last line: each is taken off where it arises,
+    so every sum stays at the scale of the data's spread, as in grad_bioen_log_posterior_base."""
+    yT = np.asarray(yTilde, dtype=np.float64)
+    f = np.asarray(forces, dtype=np.float64).reshape(-1)
+    w = get_weights_from_forces(w0, yT, f)[:, 0]
+    ybar = yT.dot(w)
+    r = ybar - np.asarray(YTilde, dtype=np.float64).reshape(-1)
+    x = yT.T.dot(f)
+    q = theta * (x - w.dot(x)) + yT.T.dot(r)
+    q -= w.dot(q)
+    dx = yT.T.dot(V)
+    dx -= w.dot(dx)[None, :]
+    c = yT.T.dot(yT.dot(w[:, None] * dx))
+    c -= w.dot(c)[None, :]
+    s = w[:, None] * (dx * (q[:, None] + theta) + c)
+    return yT.dot(s) - ybar[:, None] * s.sum(axis=0)[None, :]
+
+
+def hessp_bioen_log_posterior_base(forces, p, w0, yTilde, YTilde, theta, use_c=True):
+    """Pure-numpy Hessian-vector product H(forces) p of the negative log-posterior, p (m,) -> (m,).  Not in the
+    reference, which has no second-order information; checked against finite differences of its C gradient
+    (tests/test_forces_hessp.py).  H is the exact Hessian: symmetric, not positive definite away from the optimum."""
+    pv = np.asarray(p, dtype=np.float64).reshape(-1, 1)
+    return _hessp_base(forces, pv, w0, yTilde, YTilde, theta)[:, 0]
+
+
+def hessian_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta, use_c=True):
+    """Pure-numpy dense Hessian (m, m): the products with the m unit directions, symmetrised as (H + H^T) / 2 (the
+    products are symmetric to rounding: the asymmetry removed is below 1e-12 of the largest entry)."""
+    m = np.asarray(yTilde).shape[0]
+    H = _hessp_base(forces, np.eye(m), w0, yTilde, YTilde, theta)
+    return 0.5 * (H + H.T)
+
+
+def hessp_bioen_log_posterior(forces, p, w0, y, yTilde, YTilde, theta, use_c=True, caching=False):
+    """Hessian-vector product w.r.t. the m forces; `y` unused."""
+    if use_c:
+        return c_bioen.hessp_bioen_log_posterior_forces(forces, p, w0, yTilde, YTilde, theta)
+    return hessp_bioen_log_posterior_base(forces, p, w0, yTilde, YTilde, theta)
+
+
+def hessian_bioen_log_posterior(forces, w0, y, yTilde, YTilde, theta, use_c=True, caching=False):
+    """Dense Hessian (m, m) w.r.t. the m forces; `y` unused."""
+    if use_c:
+        return c_bioen.hessian_bioen_log_posterior_forces(forces, w0, yTilde, YTilde, theta)
+    return hessian_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta)
+
+
+# The driver that fits M unknowns with a dense Hessian.  (trust-krylov is not offered: scipy 1.15.3's failed to converge
+# on a 5-variable quartic.  newton_cg / trust_ncg stay the log-weights method's: tests/test_hessp.py pins the refusal.)
+_SCIPY_DENSE = {"trust_exact": "trust-region Newton, exact subproblem", "trust-exact": "trust-region Newton, exact subproblem"}
+
+
+def _run_scipy_trust_exact(cfg, f, fprime, hess, x0, args):
+    """scipy's trust-exact on f, f' and the dense Hessian; -> (xopt, fopt)"""
+    p = cfg["params"]
+    verbose = cfg["verbose"]
+    common.print_highlighted('method ' + _SCIPY_DENSE[cfg["algorithm"].lower()], verbose)
+    res = sopt.minimize(f, np.asarray(x0, dtype=np.float64).reshape(-1), args=args, method="trust-exact", jac=fprime,
+                        hess=hess, options={"gtol": p["gtol"], "maxiter": p["max_iterations"], "disp": bool(verbose)})
+    return res.x, res.fun
+
+
 # ------------------------------------------------------------------ optimizer
 class _DeviceFdf(object):
     """One fused device evaluation per point for scipy's separate f / f' callbacks."""
 
-    def __init__(self, w0, yTilde, YTilde, theta):
+    def __init__(self, w0, yTilde, YTilde, theta, keep_point=False):
         self.ctx, self._cached = c_bioen._context_for(yTilde, YTilde)
+        self._keep_point = keep_point       # trust-exact: every evaluation leaves the point for the products at it
         self.w0 = np.asarray(w0, dtype=np.float64).reshape(-1)
         self.theta = theta
         self._x = None
+        self._point = False       # the context keeps self._x as the point of forces_hessp
 
     def _eval(self, x):
         x = np.asarray(x, dtype=np.float64).reshape(-1)
         if self._x is None or not np.array_equal(x, self._x):
-            self._f, self._g = self.ctx.forces_fdf(x, self.w0, self.theta)
+            if self._keep_point:      # the same evaluation, same bits, and the point stays for the products at this x
+                _, self._f, self._g = self.ctx.forces_hessp(None, forces=x, w0=self.w0, theta=self.theta)
+            else:
+                self._f, self._g = self.ctx.forces_fdf(x, self.w0, self.theta)
             self._x = x.copy()
+            self._point = self._keep_point
+
+    def _set_point(self, x):
+        """the context's point is x afterwards; an x already evaluated with keep_point is not evaluated again"""
+        x = np.asarray(x, dtype=np.float64).reshape(-1)
+        if not (self._x is not None and self._point and np.array_equal(x, self._x)):
+            _, self._f, self._g = self.ctx.forces_hessp(None, forces=x, w0=self.w0, theta=self.theta)
+            self._x = x.copy()
+            self._point = True
+
+    def hessp(self, x, p, *unused):
+        """H(x) p: at the cached x the product refers to the point the context keeps (two matrix passes, like a gradient)"""
+        self._set_point(x)
+        return self.ctx.forces_hessp(np.asarray(p, dtype=np.float64).reshape(-1))
+
+    def hess(self, x, *unused):
+        """the dense Hessian at x: ceil(m / 8) batched products at the kept point"""
+        self._set_point(x)
+        return self.ctx.forces_hessian()
 
     def f(self, x, *unused):
         self._eval(x)
@@ -186,6 +284,7 @@ def _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
         print("fmin_initial", fmin_initial)
 
     forces = np.asarray(forcesInit, dtype=np.float64).copy().T    # (1, m)
+    dense = minimizer == 'SCIPY' and str(cfg["algorithm"]).lower() in _SCIPY_DENSE
 
     start = time.time()
     if minimizer in ('LIBLBFGS', 'LBFGS'):
@@ -196,15 +295,22 @@ def _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
         res = c_bioen.bioen_opt_bfgs_forces(forces, w0, yTilde, YTilde, theta, cfg)
     elif minimizer == 'SCIPY' and use_c:
         common.print_highlighted("FORCES -- Library scipy/HIP", cfg["verbose"])
-        dev = _DeviceFdf(w0, yTilde, YTilde, theta)
+        dev = _DeviceFdf(w0, yTilde, YTilde, theta, keep_point=dense)
         try:
-            res = _run_scipy(cfg, dev.f, dev.fprime, forces, (), "c", True)
+            if dense:
+                res = _run_scipy_trust_exact(cfg, dev.f, dev.fprime, dev.hess, forces, ())
+            else:
+                res = _run_scipy(cfg, dev.f, dev.fprime, forces, (), "c", True)
         finally:
             dev.close()
     else:
         common.print_highlighted("FORCES -- Library scipy/PY", cfg["verbose"])
-        res = _run_scipy(cfg, bioen_log_posterior_base, grad_bioen_log_posterior_base, forces,
-                         (w0, yTilde, YTilde, theta), "py", False)
+        if dense:
+            res = _run_scipy_trust_exact(cfg, bioen_log_posterior_base, grad_bioen_log_posterior_base,
+                                         hessian_bioen_log_posterior_base, forces, (w0, yTilde, YTilde, theta))
+        else:
+            res = _run_scipy(cfg, bioen_log_posterior_base, grad_bioen_log_posterior_base, forces,
+                             (w0, yTilde, YTilde, theta), "py", False)
     end = time.time()
     if cfg["verbose"]:
         print('time elapsed ', (end - start))
