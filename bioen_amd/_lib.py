@@ -144,6 +144,12 @@ _SIGNATURES_FORCES_HESSP = {
     "bioen_hip_forces_hessp": (C.c_int, [ctx_p, dp, dp, C.c_double, C.c_int, dp, dp, dp, dp]),
 }
 
+# every symbol include/bioen_hip_forces_gram.h declares (the third public header: the dense Hessian and the covariance of
+# the forces method in one pass); bound by lib() beside the other two
+_SIGNATURES_FORCES_GRAM = {
+    "bioen_hip_forces_gram": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp]),
+}
+
 _lib = None
 
 
@@ -153,6 +159,10 @@ def exported_symbols():
 
 def exported_symbols_forces_hessp():
     return sorted(_SIGNATURES_FORCES_HESSP)
+
+
+def exported_symbols_forces_gram():
+    return sorted(_SIGNATURES_FORCES_GRAM)
 
 
 def lib():
@@ -165,7 +175,7 @@ def lib():
                 "(or `python -c 'import __graft_entry__ as e; e.build()'`). "
                 "There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP):
+        for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP, _SIGNATURES_FORCES_GRAM):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)          # AttributeError here = header/library mismatch
                 fn.restype = res
@@ -442,10 +452,11 @@ class Context(object):
 
     def footprint(self):
         """(forms, bytes) of the resident copies of the matrix: forms is a set out of {"rowmajor", "strips", "strips_colsum"};
-        plus "bfgs_hinv" and its N x N bytes while a BFGS session (bfgs_logw) is live"""
+        plus "bfgs_hinv" and its N x N bytes while a BFGS session (bfgs_logw) is live, and "forces_gram", the device buffer
+        of forces_gram, from its first call on"""
         f, b = C.c_int(0), C.c_longlong(0)
         check(lib().bioen_hip_ctx_footprint(self._h, C.byref(f), C.byref(b)))
-        names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced", 16: "bfgs_hinv"}
+        names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced", 16: "bfgs_hinv", 32: "forces_gram"}
         return {names[k] for k in names if f.value & k}, b.value
 
     def layout(self):
@@ -752,6 +763,34 @@ class Context(object):
                                 % (asym, scale))
         H = 0.5 * (H + H.T)
         return H if out is None else (H, out[0], out[1])
+
+    def forces_gram(self, forces=None, w0=None, theta=None, cov=True, hess=True):
+        """(C, H): the covariance of the observables under the weights, C = d ybar / d forces, and the dense Hessian of the
+        forces objective (of the affine model if one is set), both (m, m) and bitwise symmetric, from ONE compute-bound
+        pass over the matrix (M <= 1024; forces_hessian builds H from 2 ceil(m / 8) bandwidth-bound ones).  A matrix not
+        asked for is None.  With `forces` (and w0, theta) the point is evaluated first, as by forces_fdf -- f and grad are
+        its bits --, and kept on the context: -> (C, H, f, grad).  Without, at the point the last such call (or
+        forces_hessp with forces) left: -> (C, H); BioenHipError (invalid state) as forces_hessp raises it.
+        The first call allocates a device buffer for the partial sums that stays with the context (footprint():
+        "forces_gram"): O(sets x m^2) whatever n is -- 117 MB at m = 256, 139 MB at m = 512, 168 MB at m = 1024 -- so with
+        many small contexts prefer forces_hessian."""
+        fn = lib().bioen_hip_forces_gram
+        m = self.m
+        C_ = np.empty((m, m)) if cov else None
+        H = np.empty((m, m)) if hess else None
+        pc, ph = (ptr(C_) if cov else None), (ptr(H) if hess else None)
+        if forces is None:
+            if not (cov or hess):
+                raise ValueError("forces_gram without forces needs cov or hess")
+            check(fn(self._h, None, None, 0.0, pc, ph, None, None))
+            return C_, H
+        if w0 is None or theta is None:
+            raise ValueError("forces_gram with forces needs w0 and theta")
+        fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
+        f = C.c_double(0.0)
+        grad = np.empty(m)
+        check(fn(self._h, ptr(fo), ptr(w0), float(theta), pc, ph, C.byref(f), ptr(grad)))
+        return C_, H, f.value, grad
 
     def forces_fdf_batch(self, forces, w0, thetas, need_grad=True):
         """K <= 8 evaluations sharing every matrix pass.  forces: (K, m), thetas: (K,) -> (f[K], grad[K, m] or None).

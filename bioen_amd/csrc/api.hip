@@ -20,6 +20,7 @@
 
 #include "ctx.hpp"
 #include "../../include/bioen_hip_forces_hessp.h"
+#include "../../include/bioen_hip_forces_gram.h"
 #include "kernels.hpp"
 #include "lbfgs.hpp"
 #include "multimin.hpp"
@@ -1106,6 +1107,7 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     bfgs_free(c);
     hessp_free(c);
+    if (c->fgram_buf) hipFree(c->fgram_buf);
     p2p_release(c);
     comm_release(c);
     resolve_timers(c);
@@ -1234,6 +1236,10 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
     if (c->bfgs) {               // the live BFGS session's inverse Hessian (api_bfgs.inl)
         f |= 16;
         b += c->bfgs_hbytes;
+    }
+    if (c->fgram_buf) {          // bioen_hip_forces_gram's sets, their sum, C and H (api_forces_gram.inl)
+        f |= 32;
+        b += c->fgram_bytes;
     }
     if (forms) *forms = f;
     if (bytes) *bytes = b;
@@ -2181,3 +2187,4 @@ static void comm_release(bioen_hip_ctx* c) {
 #include "api_bfgs.inl"
 #include "api_hessp.inl"
 #include "api_forces_hessp.inl"
+#include "api_forces_gram.inl"

@@ -137,6 +137,48 @@ static int fhp_products(bioen_hip_ctx* c, int k, const double* v, double* hv) {
     return fhp_download(c, k, hv, gm_h);
 }
 
+// Evaluates the point and keeps it on the context, for the entry `who` (this one, bioen_hip_forces_gram): the effects are
+// declared under that name, so the reason recorded for a dropped point names the call the user made.
+static int fhp_set_point(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* f, double* grad,
+                         const char* who) {
+    int rc;
+    if ((rc = enter(c, FX_EVALUATES, who))) return rc;
+    c->point_lost = "a call that failed to set a new point";
+    if ((rc = fhp_buffers(c, 0))) return rc;
+    std::vector<double> own;
+    if (!grad) {
+        own.resize((size_t)c->m);
+        grad = own.data();
+    }
+    // bioen_hip_forces_fdf's evaluation, launch for launch
+    if ((rc = forces_eval(c, 1, forces, w0, &theta, f, grad))) return rc;
+    if (strip_panels(c) ? fwd_strip_blocks(c) <= 0 : forces_fused_blocks(c) <= 0)
+        return fail(BIOEN_HIP_ESTATE, "the strip copies could not be built: the streaming kernels have no product");
+    const ProblemSlot& s0 = c->slot[0];
+    launch_fhp_keep(c, c->fpoint_ybar, c->fpoint_rs);
+    if (strip_panels(c)) {                                             // the evaluation has left w and b in the slot: no pass more
+        FhpVecArgs h{};
+        h.n = 1;
+        h.w = s0.w;
+        h.w0 = c->fixed;
+        h.b = s0.a;
+        h.pscal = s0.scal;
+        h.q = c->fpoint_q;
+        h.theta = theta;
+        launch_fhp_seg_point_q(c, h);
+    } else {
+        launch_forces_colsum(c, c->fpoint_rs, c->fpoint_q);            // b' = Y'^T (r o s): the one pass more
+        launch_fhp_point_q(c, c->fpoint_ybar, c->fpoint_rs, s0.scal, theta, s0.a, c->fpoint_q);
+    }
+    if ((rc = check_launch())) return rc;
+    BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->point_theta = theta;
+    c->point_kind = 1;
+    c->point_valid = 1;
+    c->point_lost = nullptr;
+    return 0;
+}
+
 }  // namespace bioen
 
 extern "C" int bioen_hip_forces_hessp(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, int k,
@@ -158,41 +200,10 @@ extern "C" int bioen_hip_forces_hessp(bioen_hip_ctx* c, const double* forces, co
             m = "no point on this context: call bioen_hip_forces_hessp with forces first";
         return fail(BIOEN_HIP_ESTATE, m.c_str());
     }
-    if ((rc = enter(c, forces ? FX_EVALUATES : FX_DEVICE, __func__))) return rc;      // ... with forces it is an evaluation
-    if (forces) {
-        c->point_lost = "a call that failed to set a new point";
-        if ((rc = fhp_buffers(c, 0))) return rc;
-        std::vector<double> own;
-        if (!grad) {
-            own.resize((size_t)c->m);
-            grad = own.data();
-        }
-        // bioen_hip_forces_fdf's evaluation, launch for launch
-        if ((rc = forces_eval(c, 1, forces, w0, &theta, f, grad))) return rc;
-        if (strip_panels(c) ? fwd_strip_blocks(c) <= 0 : forces_fused_blocks(c) <= 0)
-            return fail(BIOEN_HIP_ESTATE, "the strip copies could not be built: the streaming kernels have no product");
-        const ProblemSlot& s0 = c->slot[0];
-        launch_fhp_keep(c, c->fpoint_ybar, c->fpoint_rs);
-        if (strip_panels(c)) {                                             // the evaluation has left w and b in the slot: no pass more
-            FhpVecArgs h{};
-            h.n = 1;
-            h.w = s0.w;
-            h.w0 = c->fixed;
-            h.b = s0.a;
-            h.pscal = s0.scal;
-            h.q = c->fpoint_q;
-            h.theta = theta;
-            launch_fhp_seg_point_q(c, h);
-        } else {
-            launch_forces_colsum(c, c->fpoint_rs, c->fpoint_q);            // b' = Y'^T (r o s): the one pass more
-            launch_fhp_point_q(c, c->fpoint_ybar, c->fpoint_rs, s0.scal, theta, s0.a, c->fpoint_q);
-        }
-        if ((rc = check_launch())) return rc;
-        BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
-        c->point_theta = theta;
-        c->point_kind = 1;
-        c->point_valid = 1;
-        c->point_lost = nullptr;
+    if (forces) {                                                    // ... with forces it is an evaluation
+        if ((rc = fhp_set_point(c, forces, w0, theta, f, grad, __func__))) return rc;
+    } else if ((rc = enter(c, FX_DEVICE, __func__))) {
+        return rc;
     }
     if (k == 0) return 0;
     rc = fhp_products(c, k, v, hv);

@@ -299,6 +299,11 @@ struct bioen_hip_ctx {
     double* hp_vec[2 * bioen::kMaxBatch] = {};   // per direction: v | t, then the centred adjoint c, then H v (ld doubles each,
                                                  // allocated at a direction's first use, kept until the context is destroyed)
 
+    // bioen_hip_forces_gram (api_forces_gram.inl): the sets' partial Gram matrices, their sum, C and H on the device;
+    // allocated at the first call, kept until the context is destroyed (bioen_hip_ctx_footprint counts it)
+    double* fgram_buf = nullptr;
+    long long fgram_bytes = 0;
+
     // RCCL (lazy, dlopen)
     void* comm = nullptr;
     int comm_rank = 0, comm_nranks = 1;

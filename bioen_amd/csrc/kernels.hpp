@@ -186,6 +186,18 @@ void launch_forces_hp_tangent(bioen_hip_ctx* c, const struct ForcesRound& fr);  
 void launch_forces_hp_product(bioen_hip_ctx* c, const struct ForcesRound& fr);         // [matrix pass 2]
 void launch_forces_colsum(bioen_hip_ctx* c, const double* u_c, double* out);           // out = Y'^T u on the forces passes' copy
 
+// ---- dense Hessian and covariance of the forces objective in one pass (kernels_forces_gram.hip) -----------
+struct ForcesGramPlan {
+    int nsl, ntiles, nsub;          // 64-row slices, 128-row tile pairs I >= J, 64 x 64 sub-tiles of the lower triangle
+    int gs, nsets;                  // groups per canonical segment; sets of this context (local segments x gs)
+    size_t set_stride, rows_at;     // doubles per set; where a set's row sums begin
+    size_t cov_at, hess_at;         // behind the sets and their sum: C and H, m x m each
+    size_t doubles;                 // the whole buffer
+};
+ForcesGramPlan forces_gram_plan(const bioen_hip_ctx* c);
+void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
+                        const double* qv, const double* ybar, double theta);
+
 // ---- forces N-vector kernels (blockIdx.y = batch position) ---------------------------------
 struct ForcesRound {
     int n;

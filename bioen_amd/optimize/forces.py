@@ -160,6 +160,31 @@ def hessian_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta, use_c=Tr
     return 0.5 * (H + H.T)
 
 
+def hessian_gram_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta, use_c=True):
+    """(C, H), both (m, m): the covariance of the observables under the weights, C = d ybar / d forces, and the dense
+    Hessian, from two weighted, centred Gram matrices instead of m products.  With a_j = A_:j - ybar,
+    q_j = theta x_j + b_j and G[u] = sum_j u_j a_j a_j^T:
+
+      C = G[w],    H = theta C + C C + G[w (q - <q>)]
+
+    Centred like hessian_bioen_log_posterior_base, which it agrees with to rounding (tests/test_forces_gram.py); both
+    results are symmetric bit for bit."""
+    yT = np.asarray(yTilde, dtype=np.float64)
+    f = np.asarray(forces, dtype=np.float64).reshape(-1)
+    w = get_weights_from_forces(w0, yT, f)[:, 0]
+    ybar = yT.dot(w)
+    r = ybar - np.asarray(YTilde, dtype=np.float64).reshape(-1)
+    x = yT.T.dot(f)
+    q = theta * (x - w.dot(x)) + yT.T.dot(r)
+    q -= w.dot(q)
+    a = yT - ybar[:, None]
+    C = (a * w[None, :]).dot(a.T)
+    G2 = (a * (w * q)[None, :]).dot(a.T)
+    C = 0.5 * (C + C.T)
+    H = theta * C + C.dot(C) + G2
+    return C, 0.5 * (H + H.T)
+
+
 def hessp_bioen_log_posterior(forces, p, w0, y, yTilde, YTilde, theta, use_c=True, caching=False):
     """Hessian-vector product w.r.t. the m forces; `y` unused."""
     if use_c:
@@ -179,6 +204,26 @@ def hessian_bioen_log_posterior(forces, w0, y, yTilde, YTilde, theta, use_c=True
 _SCIPY_DENSE = {"trust_exact": "trust-region Newton, exact subproblem", "trust-exact": "trust-region Newton, exact subproblem"}
 
 
+# scipy:hessian -- where trust-exact's dense Hessian comes from: "products" (the default: ceil(m / 8) batched products at
+# the kept point, Context.forces_hessian) or "gram" (one compute-bound pass, Context.forces_gram; M <= 1024)
+_HESSIAN_SOURCES = ("products", "gram")
+
+
+def _hessian_source(cfg):
+    """the scipy parameter `hessian`, checked: -> "products" | "gram" """
+    source = str(cfg["params"].get("hessian", "products")).lower()
+    if source not in _HESSIAN_SOURCES:
+        raise RuntimeError("scipy:hessian=" + source + " not recognized (valid values = 'products', 'gram')")
+    if source == "gram" and str(cfg["algorithm"]).lower() not in _SCIPY_DENSE:
+        raise RuntimeError("scipy:hessian=gram serves scipy:algorithm=trust_exact only (the other drivers take no dense "
+                           "Hessian); got algorithm " + str(cfg["algorithm"]))
+    return source
+
+
+def _hess_gram_base(forces, w0, yTilde, YTilde, theta):
+    return hessian_gram_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta)[1]
+
+
 def _run_scipy_trust_exact(cfg, f, fprime, hess, x0, args):
     """scipy's trust-exact on f, f' and the dense Hessian; -> (xopt, fopt)"""
     p = cfg["params"]
@@ -193,9 +238,10 @@ def _run_scipy_trust_exact(cfg, f, fprime, hess, x0, args):
 class _DeviceFdf(object):
     """One fused device evaluation per point for scipy's separate f / f' callbacks."""
 
-    def __init__(self, w0, yTilde, YTilde, theta, keep_point=False):
+    def __init__(self, w0, yTilde, YTilde, theta, keep_point=False, hessian="products"):
         self.ctx, self._cached = c_bioen._context_for(yTilde, YTilde)
         self._keep_point = keep_point       # trust-exact: every evaluation leaves the point for the products at it
+        self._hessian = hessian             # "gram": the dense Hessian from Context.forces_gram
         self.w0 = np.asarray(w0, dtype=np.float64).reshape(-1)
         self.theta = theta
         self._x = None
@@ -225,8 +271,10 @@ class _DeviceFdf(object):
         return self.ctx.forces_hessp(np.asarray(p, dtype=np.float64).reshape(-1))
 
     def hess(self, x, *unused):
-        """the dense Hessian at x: ceil(m / 8) batched products at the kept point"""
+        """the dense Hessian at x: ceil(m / 8) batched products at the kept point, or (scipy:hessian=gram) one Gram pass"""
         self._set_point(x)
+        if self._hessian == "gram":
+            return self.ctx.forces_gram(cov=False)[1]
         return self.ctx.forces_hessian()
 
     def f(self, x, *unused):
@@ -252,6 +300,8 @@ def find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
     if str(cfg["minimizer"]).upper() == 'SCIPY' and cfg["params"].get("on_device"):
         raise RuntimeError("scipy:on_device (scipy's BFGS with the inverse Hessian on the device) serves the "
                            "log-weights method only (optimize.log_weights.find_optimum); the forces method has none")
+    if str(cfg["minimizer"]).upper() == 'SCIPY':
+        _hessian_source(cfg)
     if not (str(cfg["minimizer"]).upper() == 'SCIPY' and not bool(cfg["use_c_functions"])):
         with c_bioen.hold(yTilde, YTilde):
             return _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg)
@@ -285,6 +335,7 @@ def _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
 
     forces = np.asarray(forcesInit, dtype=np.float64).copy().T    # (1, m)
     dense = minimizer == 'SCIPY' and str(cfg["algorithm"]).lower() in _SCIPY_DENSE
+    hessian = _hessian_source(cfg) if minimizer == 'SCIPY' else "products"
 
     start = time.time()
     if minimizer in ('LIBLBFGS', 'LBFGS'):
@@ -295,7 +346,7 @@ def _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
         res = c_bioen.bioen_opt_bfgs_forces(forces, w0, yTilde, YTilde, theta, cfg)
     elif minimizer == 'SCIPY' and use_c:
         common.print_highlighted("FORCES -- Library scipy/HIP", cfg["verbose"])
-        dev = _DeviceFdf(w0, yTilde, YTilde, theta, keep_point=dense)
+        dev = _DeviceFdf(w0, yTilde, YTilde, theta, keep_point=dense, hessian=hessian)
         try:
             if dense:
                 res = _run_scipy_trust_exact(cfg, dev.f, dev.fprime, dev.hess, forces, ())
@@ -307,7 +358,8 @@ def _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
         common.print_highlighted("FORCES -- Library scipy/PY", cfg["verbose"])
         if dense:
             res = _run_scipy_trust_exact(cfg, bioen_log_posterior_base, grad_bioen_log_posterior_base,
-                                         hessian_bioen_log_posterior_base, forces, (w0, yTilde, YTilde, theta))
+                                         _hess_gram_base if hessian == "gram" else hessian_bioen_log_posterior_base,
+                                         forces, (w0, yTilde, YTilde, theta))
         else:
             res = _run_scipy(cfg, bioen_log_posterior_base, grad_bioen_log_posterior_base, forces,
                              (w0, yTilde, YTilde, theta), "py", False)
