@@ -721,6 +721,11 @@ static int eval_logw_point(bioen_hip_ctx* c, const Round& r, bool with_grad, boo
     return 0;
 }
 
+// what a sharded context is told when the forces method finds no strip copies (BIOEN_HIP_PANELS=0, more than kMaxPanels
+// row panels: M > 16384, or no memory for them): the streaming kernels' partial sums are not in canonical segments
+static const char kForcesNeedsStrips[] =
+    "the forces method on a sharded context needs the strip copies of the matrix (M > 1024: the row panels, at most 16: M <= 16384)";
+
 // forces: um holds the forces of the round's K problems, compact [row*K + a]
 static ForcesRound make_forces_round(bioen_hip_ctx* c, const int* slots, int k, const double* theta) {
     ForcesRound r{};
@@ -838,8 +843,8 @@ static int enqueue_forces_eval(bioen_hip_ctx* c, const ForcesRound& fr, const Ro
         }
         return 0;
     }
-    if (c->world != 1)      // (no strip copies: switched off by the environment, or no memory for them)
-        return fail(BIOEN_HIP_ESTATE, "the forces method on a sharded context needs the strip copies of the matrix (M > 1024: the row panels)");
+    if (c->world != 1)      // (the copies were lost to an allocation inside this call; forces_guard refuses every other case)
+        return fail(BIOEN_HIP_ESTATE, kForcesNeedsStrips);
     if ((rc = enqueue_forces_weights(c, fr))) return rc;
     Vec8 v{};
     for (int a = 0; a < fr.n; ++a) v.p[a] = fr.w[a];
@@ -1433,7 +1438,7 @@ static bool forces_canonical(const bioen_hip_ctx* c) {
 static int forces_guard(const bioen_hip_ctx* c, bool strip_path_ok = true) {
     // sharded contexts run the forces method in canonical segments only (not on the r01 streaming kernels)
     if (c->world != 1 && !(strip_path_ok && forces_canonical(c)))
-        return fail(BIOEN_HIP_ESTATE, "not available on this structure-sharded context");
+        return fail(BIOEN_HIP_ESTATE, strip_path_ok ? kForcesNeedsStrips : "not available on this structure-sharded context");
     if (is_affine(c) && c->storage)          // the experiment's copies are pre-centred and its passes carry no offset
         return fail(BIOEN_HIP_ESTATE, "the affine observable model is not served on the reduced-storage experiment's copies "
                                       "(bioen_hip_ctx_set_storage(0), or remove the model)");

@@ -131,7 +131,16 @@ __global__ __launch_bounds__(kBlock) void k_fhp_seg_t(FhpVecArgs h, int n, Xch x
     const double dxbar = PRODUCT ? h.scal[a][S_SPARE0] : 0.0, b0 = PRODUCT ? h.scal[a][S_B0] : 0.0;
     double s = 0.0;
     const SegPos sp = seg_pos(xo.npl, xo.segcols, n);
-    for (int j = seg_first(sp); j < sp.jend; j += seg_step(xo.npl)) {
+    // The walk covers the WHOLE segment, padding included, as k_hessp_tangent's: t is one of the buffers the log-weights
+    // products use, whose adjoint pass leaves its constant beyond column n, and the row-sum pass multiplies the padding
+    // with the centred operand (0 - centre) -- the first product after a bioen_hip_logw_hessp call on the same context
+    // was wrong by that (tests/test_hip_panel_loops.py: 16384 x 300).  Every pair past the valid columns is written as zero.
+    const int jseg = sp.j0 + xo.segcols;
+    for (int j = seg_first(sp); j < jseg; j += seg_step(xo.npl)) {
+        if (j >= sp.jend) {
+            *reinterpret_cast<d2*>(t + j) = d2{0.0, 0.0};
+            continue;
+        }
         const d2 wv = ld_vec(h.w + j), dv = ld_vec(dx + j);
         const bool two = j + 1 < sp.jend;
         d2 tv;

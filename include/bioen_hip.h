@@ -123,6 +123,10 @@ int bioen_hip_ctx_create_synthetic(int m, int n, const double* YTrue, const doub
  * opt_lbfgs_logw(_batch), opt_gsl_logw, and the forces method (forces_weights, forces_fdf(_batch),
  * opt_lbfgs_forces(_batch), opt_gsl_forces) for every M served by strip copies (M <= 1024: two passes; beyond: four
  * passes over row panels).
+ * The strip kernels serve M <= 16 x 1024 = 16384: at most 16 row panels.  Beyond that the streaming kernels on the
+ * row-major matrix serve the context (the log-weights method, and the forces method on unsharded contexts only:
+ * BIOEN_HIP_ESTATE on a sharded one), and the Hessian-vector products of the forces objective (bioen_hip_forces_hessp;
+ * bioen_hip_forces_gram serves M <= 1024) are refused with BIOEN_HIP_ESTATE.
  * Minimum size: the LAST rank must still own a column, (world - 1) * P < n -- n > 512 for two ranks, > 768 for four,
  * > 896 for eight (S is at least 128); BIOEN_HIP_EINVAL ("too few structures to shard") on EVERY rank otherwise, so that
  * none waits in a collective for one that failed.  The leading dimension of the local data is segments-per-rank * S. */

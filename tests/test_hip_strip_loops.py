@@ -78,9 +78,9 @@ def bioen_amd():
 
 
 # ---- regimes ---------------------------------------------------------------------------------------------------------
-def enter_regime(monkeypatch, shape):
-    """the environment a shape's contexts are created in"""
-    if REGIMES[shape]["segments"] == 1:
+def enter_regime(monkeypatch, shape, regimes=None):
+    """the environment a shape's contexts are created in (regimes: another file's table, tests/test_hip_panel_loops.py)"""
+    if (regimes or REGIMES)[shape]["segments"] == 1:
         monkeypatch.setenv("BIOEN_HIP_SEGMENTS", "1")
 
 
@@ -99,8 +99,8 @@ def assert_forces_regime(ctx, shape, local_segments=None):
     return p
 
 
-def assert_forward_regime(ctx, shape, fold=None, local_segments=None):
-    want, p = REGIMES[shape], ctx.strip_plan(0)
+def assert_forward_regime(ctx, shape, fold=None, local_segments=None, regimes=None):
+    want, p = (regimes or REGIMES)[shape], ctx.strip_plan(0)
     gs, tc, nch, dflt_fold = want["forward"]
     assert p["local_segments"] == (want["segments"] if local_segments is None else local_segments), p
     assert (p["gs"], p["tc"], p["nch"]) == (gs, tc, nch), p
@@ -116,7 +116,7 @@ def assert_forward_regime(ctx, shape, fold=None, local_segments=None):
 
 
 # ---- data and the truth, once per shape ------------------------------------------------------------------------------
-_DATA, _FORCES_TRUTH, _LOGW_TRUTH, _DEFAULT_BITS = {}, {}, {}, {}
+_DATA, _FORCES_TRUTH, _FORCES_YBAR, _LOGW_TRUTH, _DEFAULT_BITS = {}, {}, {}, {}, {}
 
 
 def data(shape):
@@ -166,11 +166,18 @@ def forces_truth(shape):
 
         def cond():
             return (np.abs(yT.astype(L) - Yl[:, None]) @ np.abs(t) + np.abs(r) * abs(t.sum())).astype(np.float64)
-        return float(obj), grad.astype(np.float64), cond
+        return float(obj), grad.astype(np.float64), cond, ybar.astype(np.float64)
     with ThreadPoolExecutor(8) as pool:                         # (numpy's longdouble products release the interpreter lock)
         out = list(pool.map(one, SCALES, THETAS))
-    _FORCES_TRUTH[shape] = out
-    return out
+    _FORCES_TRUTH[shape] = [o[:3] for o in out]
+    _FORCES_YBAR[shape] = [o[3] for o in out]
+    return _FORCES_TRUTH[shape]
+
+
+def forces_average_truth(shape):
+    """yTilde . w of the eight problems, from the same 80-bit evaluation (Context.last_average is held to it)"""
+    forces_truth(shape)
+    return _FORCES_YBAR[shape]
 
 
 def logw_problem(shape):
