@@ -150,6 +150,12 @@ _SIGNATURES_FORCES_GRAM = {
     "bioen_hip_forces_gram": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp]),
 }
 
+# every symbol include/bioen_hip_forces_colquad.h declares (the fourth public header: one quadratic form per structure at
+# a kept forces point); bound by lib() beside the other three
+_SIGNATURES_FORCES_COLQUAD = {
+    "bioen_hip_forces_colquad": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp]),
+}
+
 _lib = None
 
 
@@ -165,6 +171,10 @@ def exported_symbols_forces_gram():
     return sorted(_SIGNATURES_FORCES_GRAM)
 
 
+def exported_symbols_forces_colquad():
+    return sorted(_SIGNATURES_FORCES_COLQUAD)
+
+
 def lib():
     """Load libbioen_hip.so (once).  Raises if it has not been built."""
     global _lib
@@ -175,7 +185,7 @@ def lib():
                 "(or `python -c 'import __graft_entry__ as e; e.build()'`). "
                 "There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP, _SIGNATURES_FORCES_GRAM):
+        for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP, _SIGNATURES_FORCES_GRAM, _SIGNATURES_FORCES_COLQUAD):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)          # AttributeError here = header/library mismatch
                 fn.restype = res
@@ -453,10 +463,11 @@ class Context(object):
     def footprint(self):
         """(forms, bytes) of the resident copies of the matrix: forms is a set out of {"rowmajor", "strips", "strips_colsum"};
         plus "bfgs_hinv" and its N x N bytes while a BFGS session (bfgs_logw) is live, and "forces_gram", the device buffer
-        of forces_gram, from its first call on"""
+        of forces_gram, and "forces_colquad", the one of forces_colquad, each from its first call on"""
         f, b = C.c_int(0), C.c_longlong(0)
         check(lib().bioen_hip_ctx_footprint(self._h, C.byref(f), C.byref(b)))
-        names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced", 16: "bfgs_hinv", 32: "forces_gram"}
+        names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced", 16: "bfgs_hinv", 32: "forces_gram",
+                 64: "forces_colquad"}
         return {names[k] for k in names if f.value & k}, b.value
 
     def layout(self):
@@ -791,6 +802,36 @@ class Context(object):
         grad = np.empty(m)
         check(fn(self._h, ptr(fo), ptr(w0), float(theta), pc, ph, C.byref(f), ptr(grad)))
         return C_, H, f.value, grad
+
+    def forces_colquad(self, P, forces=None, w0=None, theta=None):
+        """v[j] = a_j^T P a_j for every structure j, a_j = y_j - ybar the structure's observables (of the affine model if one
+        is set) centred on the averages under the point's weights, P a symmetric (m, m) matrix: ONE compute-bound pass
+        over the matrix (M <= 1024).  Since d ln w_j / d forces = a_j, P = inv(H) gives the Laplace variance of ln w_j
+        (forces.laplace_error_bars), P = inv(C) a structure's Mahalanobis distance from the refined ensemble, P = I its
+        spread.  With `forces` (and w0, theta) the point is evaluated first, as by forces_fdf -- f and grad are its bits --,
+        and kept on the context: -> (v, f, grad).  Without, at the point the last such call (or forces_hessp / forces_gram
+        with forces) left: -> v; BioenHipError (invalid state) as forces_hessp raises it.  ValueError for a P of the wrong
+        shape or one that is not symmetric (|P_ij - P_ji| > 1e-12 max |P|).  The first call allocates a device buffer of
+        16-padded m^2 + n doubles that stays with the context (footprint(): "forces_colquad")."""
+        fn = lib().bioen_hip_forces_colquad
+        m = self.m
+        Pa = as_f64(P)
+        if Pa.shape != (m, m):
+            raise ValueError("P must be (M, M) with M = %d, got %s" % (m, (Pa.shape,)))
+        if np.abs(Pa - Pa.T).max() > 1e-12 * np.abs(Pa).max():      # (the entry's own gate; non-finite entries pass, as there)
+            raise ValueError("P is not symmetric: max |P - P^T| = %.3g, max |P| = %.3g"
+                             % (np.abs(Pa - Pa.T).max(), np.abs(Pa).max()))
+        v = np.empty(self.n)
+        if forces is None:
+            check(fn(self._h, None, None, 0.0, ptr(Pa), ptr(v), None, None))
+            return v
+        if w0 is None or theta is None:
+            raise ValueError("forces_colquad with forces needs w0 and theta")
+        fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
+        f = C.c_double(0.0)
+        grad = np.empty(m)
+        check(fn(self._h, ptr(fo), ptr(w0), float(theta), ptr(Pa), ptr(v), C.byref(f), ptr(grad)))
+        return v, f.value, grad
 
     def forces_fdf_batch(self, forces, w0, thetas, need_grad=True):
         """K <= 8 evaluations sharing every matrix pass.  forces: (K, m), thetas: (K,) -> (f[K], grad[K, m] or None).

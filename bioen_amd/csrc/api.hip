@@ -21,6 +21,7 @@
 #include "ctx.hpp"
 #include "../../include/bioen_hip_forces_hessp.h"
 #include "../../include/bioen_hip_forces_gram.h"
+#include "../../include/bioen_hip_forces_colquad.h"
 #include "kernels.hpp"
 #include "lbfgs.hpp"
 #include "multimin.hpp"
@@ -1113,6 +1114,7 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
     bfgs_free(c);
     hessp_free(c);
     if (c->fgram_buf) hipFree(c->fgram_buf);
+    if (c->fcolquad_buf) hipFree(c->fcolquad_buf);
     p2p_release(c);
     comm_release(c);
     resolve_timers(c);
@@ -1245,6 +1247,10 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
     if (c->fgram_buf) {          // bioen_hip_forces_gram's sets, their sum, C and H (api_forces_gram.inl)
         f |= 32;
         b += c->fgram_bytes;
+    }
+    if (c->fcolquad_buf) {       // bioen_hip_forces_colquad's P and results (api_forces_colquad.inl)
+        f |= 64;
+        b += c->fcolquad_bytes;
     }
     if (forms) *forms = f;
     if (bytes) *bytes = b;
@@ -2193,3 +2199,4 @@ static void comm_release(bioen_hip_ctx* c) {
 #include "api_hessp.inl"
 #include "api_forces_hessp.inl"
 #include "api_forces_gram.inl"
+#include "api_forces_colquad.inl"

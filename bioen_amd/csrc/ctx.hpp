@@ -304,6 +304,11 @@ struct bioen_hip_ctx {
     double* fgram_buf = nullptr;
     long long fgram_bytes = 0;
 
+    // bioen_hip_forces_colquad (api_forces_colquad.inl): P_eff padded to the strip rows, then the n results; allocated at
+    // the first call, kept until the context is destroyed (bioen_hip_ctx_footprint counts it)
+    double* fcolquad_buf = nullptr;
+    long long fcolquad_bytes = 0;
+
     // RCCL (lazy, dlopen)
     void* comm = nullptr;
     int comm_rank = 0, comm_nranks = 1;

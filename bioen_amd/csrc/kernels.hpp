@@ -198,6 +198,12 @@ ForcesGramPlan forces_gram_plan(const bioen_hip_ctx* c);
 void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
                         const double* qv, const double* ybar, double theta);
 
+// ---- per-structure quadratic forms a_j^T P a_j at a kept forces point (kernels_forces_colquad.hip) -----------
+constexpr int kForcesColquadCols = 32;      // columns of a panel: one block owns them and all M rows
+constexpr int kForcesColquadBlocks = 256;   // blocks of a launch (one per CU); block b runs the panels b, b + 256, ...
+// P: (strip rows)^2 doubles, zero beyond m, symmetric; ybar: the point's ybar'; out: n values
+void launch_forces_colquad(bioen_hip_ctx* c, const double* P, const double* ybar, double* out);
+
 // ---- forces N-vector kernels (blockIdx.y = batch position) ---------------------------------
 struct ForcesRound {
     int n;

@@ -199,6 +199,80 @@ def hessian_bioen_log_posterior(forces, w0, y, yTilde, YTilde, theta, use_c=True
     return hessian_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta)
 
 
+# ------------------------------------------------------------------ Laplace error bars
+def colquad_bioen_log_posterior_base(forces, P, w0, yTilde, YTilde, theta, use_c=True):
+    """Pure-numpy v (n,): v_j = a_j^T P a_j with a_j = A_:j - ybar at the weights of `forces` and P (m, m) symmetric -- the
+    restatement of Context.forces_colquad.  d ln w_j / d forces = a_j, so with P = inv(H) this is the Laplace
+    variance of ln w_j.  The operand is centred first; the quadratic is not expanded."""
+    yT = np.asarray(yTilde, dtype=np.float64)
+    f = np.asarray(forces, dtype=np.float64).reshape(-1)
+    Pm = np.asarray(P, dtype=np.float64)
+    if Pm.shape != (yT.shape[0], yT.shape[0]):
+        raise ValueError("P must be (M, M) with M = %d, got %s" % (yT.shape[0], (Pm.shape,)))
+    w = get_weights_from_forces(w0, yT, f)[:, 0]
+    a = yT - yT.dot(w)[:, None]
+    return (Pm.dot(a) * a).sum(axis=0)
+
+
+def _laplace_inverse(H, theta):
+    """inv(H) through a Cholesky factorisation; ValueError, saying which of the two it found, if H is not positive
+    definite: indefinite (away from a minimum) or singular to rounding (C singular, always so for N <= M)"""
+    scale = float(np.abs(H).max())
+    try:
+        L = np.linalg.cholesky(H)
+        definite = float(np.diag(L).min()) ** 2 > 1e-13 * scale          # (a pivot at rounding: the factorisation got through by luck)
+    except np.linalg.LinAlgError:
+        definite = False
+    if not definite:
+        lo = float(np.linalg.eigvalsh(H)[0])
+        # H = theta C + C C + G2: at a minimum its smallest eigenvalue is >= theta x that of C, so one within rounding of
+        # zero on the scale of theta and of H says C is singular; a clearly negative one says this is no minimum
+        if lo < -1e-8 * max(abs(theta), scale):
+            raise ValueError("laplace_error_bars: the Hessian is indefinite (smallest eigenvalue %.3g): the forces are not "
+                             "at a minimum of the objective" % lo)
+        raise ValueError("laplace_error_bars: the Hessian is singular (smallest eigenvalue %.3g against theta = %.3g): the "
+                         "covariance of the observables is singular, as it always is for N <= M" % (lo, theta))
+    Li = np.linalg.solve(L, np.eye(H.shape[0]))
+    Hi = Li.T.dot(Li)
+    return 0.5 * (Hi + Hi.T)
+
+
+def laplace_error_bars(forces, w0, y, yTilde, YTilde, theta, use_c=True, caching=False):
+    """Laplace error bars at an optimum `forces` of the forces objective, the negative log-posterior L = theta KL + chi^2 / 2:
+    the forces are Gaussian around it with covariance inv(H), and d ybar / d forces = C, d ln w_j / d forces = a_j.  -> dict:
+
+      w (n,), C (m, m), H (m, m)
+      cov_forces = inv(H), std_forces                  (m, m), (m,)
+      cov_averages = C inv(H) C, std_averages          (m, m), (m,)   of ybar in the units of yTilde
+      var_logw (n,): a_j^T inv(H) a_j,  std_w = w sqrt(var_logw)
+
+    use_c: C and H from Context.forces_gram and var_logw from Context.forces_colquad at one kept point of a resident
+    context (M <= 1024); else the numpy restatements.  ValueError if H is not positive definite.  `y` unused."""
+    f = np.asarray(forces, dtype=np.float64).reshape(-1)
+    w0v = np.asarray(w0, dtype=np.float64).reshape(-1)
+    if use_c:
+        ctx, cached = c_bioen._context_for(yTilde, YTilde)
+        try:
+            C, H, _, _ = ctx.forces_gram(forces=f, w0=w0v, theta=theta)
+            Hi = _laplace_inverse(H, theta)
+            var_logw = ctx.forces_colquad(Hi)
+            w = np.asarray(ctx.forces_weights(f, w0v), dtype=np.float64).reshape(-1)      # (an evaluation: the point goes)
+        finally:
+            c_bioen._release(ctx, cached)
+    else:
+        C, H = hessian_gram_bioen_log_posterior_base(f, w0v, yTilde, YTilde, theta)
+        Hi = _laplace_inverse(H, theta)
+        var_logw = colquad_bioen_log_posterior_base(f, Hi, w0v, yTilde, YTilde, theta)
+        w = get_weights_from_forces(w0v, np.asarray(yTilde, dtype=np.float64), f)[:, 0]
+    cov_av = C.dot(Hi).dot(C)
+    cov_av = 0.5 * (cov_av + cov_av.T)
+    var_logw = np.maximum(var_logw, 0.0)
+    return {"w": w, "C": C, "H": H,
+            "cov_forces": Hi, "std_forces": np.sqrt(np.diag(Hi)),
+            "cov_averages": cov_av, "std_averages": np.sqrt(np.maximum(np.diag(cov_av), 0.0)),
+            "var_logw": var_logw, "std_w": w * np.sqrt(var_logw)}
+
+
 # The driver that fits M unknowns with a dense Hessian.  (trust-krylov is not offered: scipy 1.15.3's failed to converge
 # on a 5-variable quartic.  newton_cg / trust_ncg stay the log-weights method's: tests/test_hessp.py pins the refusal.)
 _SCIPY_DENSE = {"trust_exact": "trust-region Newton, exact subproblem", "trust-exact": "trust-region Newton, exact subproblem"}

@@ -172,6 +172,7 @@ int bioen_hip_ctx_read_ytilde(bioen_hip_ctx* ctx, int row0, int rows, int col0, 
  * from the two-copy default: the sums over rows are formed in another order). */
 /* (bit 3: copies of the reduced-storage experiment, bioen_hip_ctx_set_storage, beside the FP64 row-major matrix) */
 /* (bit 5: the device buffer of bioen_hip_forces_gram, bioen_hip_forces_gram.h, from its first call on) */
+/* (bit 6: the device buffer of bioen_hip_forces_colquad, bioen_hip_forces_colquad.h, from its first call on) */
 int bioen_hip_ctx_footprint(const bioen_hip_ctx* ctx, int* forms, long long* bytes);
 /* r06: HOW the strip copies are held.  one_copy: 1 = the log-weights adjoint runs on the row-sum order copy (asked for, or
  * taken by THIS rank because the second copy could not be allocated -- its last bits then differ from a two-copy rank's:
