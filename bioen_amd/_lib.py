@@ -156,6 +156,12 @@ _SIGNATURES_FORCES_COLQUAD = {
     "bioen_hip_forces_colquad": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp]),
 }
 
+# every symbol include/bioen_hip_forces_gram_bf16.h declares (the fifth public header: the forces Hessian for a Newton
+# minimizer from split-BF16 operands); bound by lib() beside the other four
+_SIGNATURES_FORCES_GRAM_BF16 = {
+    "bioen_hip_forces_gram_bf16": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp]),
+}
+
 _lib = None
 
 
@@ -175,6 +181,10 @@ def exported_symbols_forces_colquad():
     return sorted(_SIGNATURES_FORCES_COLQUAD)
 
 
+def exported_symbols_forces_gram_bf16():
+    return sorted(_SIGNATURES_FORCES_GRAM_BF16)
+
+
 def lib():
     """Load libbioen_hip.so (once).  Raises if it has not been built."""
     global _lib
@@ -185,7 +195,8 @@ def lib():
                 "(or `python -c 'import __graft_entry__ as e; e.build()'`). "
                 "There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP, _SIGNATURES_FORCES_GRAM, _SIGNATURES_FORCES_COLQUAD):
+        for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP, _SIGNATURES_FORCES_GRAM, _SIGNATURES_FORCES_COLQUAD,
+                      _SIGNATURES_FORCES_GRAM_BF16):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)          # AttributeError here = header/library mismatch
                 fn.restype = res
@@ -463,11 +474,12 @@ class Context(object):
     def footprint(self):
         """(forms, bytes) of the resident copies of the matrix: forms is a set out of {"rowmajor", "strips", "strips_colsum"};
         plus "bfgs_hinv" and its N x N bytes while a BFGS session (bfgs_logw) is live, and "forces_gram", the device buffer
-        of forces_gram, and "forces_colquad", the one of forces_colquad, each from its first call on"""
+        of forces_gram, "forces_colquad", the one of forces_colquad, and "forces_gram_bf16", the one of forces_gram_bf16, each from its first
+        call on"""
         f, b = C.c_int(0), C.c_longlong(0)
         check(lib().bioen_hip_ctx_footprint(self._h, C.byref(f), C.byref(b)))
         names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced", 16: "bfgs_hinv", 32: "forces_gram",
-                 64: "forces_colquad"}
+                 64: "forces_colquad", 128: "forces_gram_bf16"}
         return {names[k] for k in names if f.value & k}, b.value
 
     def layout(self):
@@ -797,6 +809,34 @@ class Context(object):
             return C_, H
         if w0 is None or theta is None:
             raise ValueError("forces_gram with forces needs w0 and theta")
+        fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
+        f = C.c_double(0.0)
+        grad = np.empty(m)
+        check(fn(self._h, ptr(fo), ptr(w0), float(theta), pc, ph, C.byref(f), ptr(grad)))
+        return C_, H, f.value, grad
+
+    def forces_gram_bf16(self, forces=None, w0=None, theta=None, cov=True, hess=True):
+        """(C~, H~): forces_gram's C and H with the two M x M x N products formed from split-BF16 operands (every operand
+        hi + lo, two bfloat16 numbers; hi hi + hi lo + lo hi accumulated in f32) on the BF16 matrix cores, at 32 x the FP64
+        matrix rate (M <= 1024).  The result is a MINIMIZER's Hessian, good to about 1e-5 ... 1e-4 of max|H|: it
+        shapes a Newton step (scipy:hessian=gram_bf16), while f and grad stay forces_fdf's FP64 bits and decide the
+        optimum.  laplace_error_bars keeps using forces_gram, whose results this call leaves bitwise alone.  Arguments,
+        return shapes, point semantics and refusals are forces_gram's: with `forces` (and w0, theta) -> (C~, H~, f, grad) and
+        the point is kept; without -> (C~, H~) at the kept point.  Both matrices are bitwise symmetric and the same bits
+        call after call.  The first computing call allocates a device buffer of forces_gram's size that stays with the
+        context (footprint(): "forces_gram_bf16")."""
+        fn = lib().bioen_hip_forces_gram_bf16
+        m = self.m
+        C_ = np.empty((m, m)) if cov else None
+        H = np.empty((m, m)) if hess else None
+        pc, ph = (ptr(C_) if cov else None), (ptr(H) if hess else None)
+        if forces is None:
+            if not (cov or hess):
+                raise ValueError("forces_gram_bf16 without forces needs cov or hess")
+            check(fn(self._h, None, None, 0.0, pc, ph, None, None))
+            return C_, H
+        if w0 is None or theta is None:
+            raise ValueError("forces_gram_bf16 with forces needs w0 and theta")
         fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
         f = C.c_double(0.0)
         grad = np.empty(m)

@@ -22,6 +22,7 @@
 #include "../../include/bioen_hip_forces_hessp.h"
 #include "../../include/bioen_hip_forces_gram.h"
 #include "../../include/bioen_hip_forces_colquad.h"
+#include "../../include/bioen_hip_forces_gram_bf16.h"
 #include "kernels.hpp"
 #include "lbfgs.hpp"
 #include "multimin.hpp"
@@ -1115,6 +1116,7 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
     hessp_free(c);
     if (c->fgram_buf) hipFree(c->fgram_buf);
     if (c->fcolquad_buf) hipFree(c->fcolquad_buf);
+    if (c->fgram16_buf) hipFree(c->fgram16_buf);
     p2p_release(c);
     comm_release(c);
     resolve_timers(c);
@@ -1251,6 +1253,10 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
     if (c->fcolquad_buf) {       // bioen_hip_forces_colquad's P and results (api_forces_colquad.inl)
         f |= 64;
         b += c->fcolquad_bytes;
+    }
+    if (c->fgram16_buf) {        // bioen_hip_forces_gram_bf16's sets, their sum, C~ and H~ (api_forces_gram_bf16.inl)
+        f |= 128;
+        b += c->fgram16_bytes;
     }
     if (forms) *forms = f;
     if (bytes) *bytes = b;
@@ -2200,3 +2206,4 @@ static void comm_release(bioen_hip_ctx* c) {
 #include "api_forces_hessp.inl"
 #include "api_forces_gram.inl"
 #include "api_forces_colquad.inl"
+#include "api_forces_gram_bf16.inl"

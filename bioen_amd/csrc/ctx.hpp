@@ -309,6 +309,12 @@ struct bioen_hip_ctx {
     double* fcolquad_buf = nullptr;
     long long fcolquad_bytes = 0;
 
+    // bioen_hip_forces_gram_bf16 (api_forces_gram_bf16.inl): the split-BF16 pass's sets, their sum, C~ and H~ -- a buffer of
+    // its own beside fgram_buf (the FP64 pass's results stay what they are); allocated at the first computing call, kept
+    // until the context is destroyed (bioen_hip_ctx_footprint counts it)
+    double* fgram16_buf = nullptr;
+    long long fgram16_bytes = 0;
+
     // RCCL (lazy, dlopen)
     void* comm = nullptr;
     int comm_rank = 0, comm_nranks = 1;

@@ -198,6 +198,11 @@ ForcesGramPlan forces_gram_plan(const bioen_hip_ctx* c);
 void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
                         const double* qv, const double* ybar, double theta);
 
+// the same pass with split-BF16 operands on the BF16 matrix cores (kernels_forces_gram_bf16.hip): the plan, the
+// sets' layout and the finishing kernels are the FP64 pass's, buf is a buffer of its own
+void launch_forces_gram_bf16(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
+                             const double* qv, const double* ybar, double theta);
+
 // ---- per-structure quadratic forms a_j^T P a_j at a kept forces point (kernels_forces_colquad.hip) -----------
 constexpr int kForcesColquadCols = 32;      // columns of a panel: one block owns them and all M rows
 constexpr int kForcesColquadBlocks = 256;   // blocks of a launch (one per CU); block b runs the panels b, b + 256, ...

@@ -1,0 +1,246 @@
+// Forces method, M <= 1024: the dense Hessian for a Newton minimizer from SPLIT-BF16 operands on the BF16 matrix cores
+// (gfx950).  The mathematics, the sets, their order and the layout of what a set leaves are k_forces_gram's
+// (kernels_forces_gram.hip); only the two M x M x N products change precision:
+//   a = Y_ij - centre_i (FP64)        a_hi = bf(a),  a_lo = bf((float)a - a_hi)          bf: float, then bfloat16, both
+//   t = a u_j           (FP64)        t_hi = bf(t),  t_lo = bf((float)t - t_hi)              round-to-nearest-even
+//   G'[u]_ik = sum_j (a_hi t_hi + a_hi t_lo + a_lo t_hi)        v_mfma_f32_16x16x16_bf16, f32 accumulators
+// The row sums g = sum_j u2_j Y'_j stay k_forces_gram's FP64 fma chains (they feed a cancellation): the same bits.
+//
+// The strip copy's registers (row = lane & 15, the strip's columns 4 qq + (lane >> 4) in qq = 0 .. 3) are a 16-row, 16-deep
+// BF16 operand as they stand: element qq of a lane's fragment is depth index 4 (lane >> 4) + qq of the instruction, for the A
+// and the B operand alike, so the instruction contracts over the strip's 16 columns in a permuted order.  A wave owns a
+// 64 x 64 sub-tile of both matrices (2 x 16 accumulators of 4 floats), a block of four waves a 128 x 128 tile pair I >= J, as
+// in k_forces_gram.  A set's f32 sums leave as doubles on k_forces_gram's layout, so the sets are added IN FP64 in its
+// fixed order by its k_fgram_sum_sets, and k_fgram_finish / k_fgram_square finish them: those three kernels are launched
+// from here as they are.
+#include "strip.hpp"
+
+namespace bioen {
+
+typedef float fl4 __attribute__((ext_vector_type(4)));
+typedef short bh4 __attribute__((ext_vector_type(4)));      // four bfloat16: an operand fragment of the 16-deep instruction
+typedef unsigned u2v __attribute__((ext_vector_type(2)));   // the same two registers as they are filled: elements (0, 1) | (2, 3)
+
+// kernels_forces_gram.hip's: the sets' sum and the finishing steps
+__global__ void k_fgram_sum_sets(const double* __restrict__ partial, size_t set_stride, size_t count, int nlocal, int gs,
+                                 double* __restrict__ out);
+__global__ void k_fgram_finish(const double* __restrict__ sum, size_t rows_at, int m, double theta, const double* __restrict__ ybar,
+                               const double* __restrict__ row_scale, bool affine, double* __restrict__ cov,
+                               double* __restrict__ hess);
+__global__ void k_fgram_square(const double* __restrict__ cov, int m, double* __restrict__ hess);
+
+constexpr int kFGram16SubDoubles = 2 * 16 * 4 * 64;     // = kFGramSubDoubles: [matrix 2][h 4][g 4][register 4][lane 64]
+
+struct FGram16Args {
+    const double* Ys;       // row-sum order strip copy
+    const double* center;   // mp values
+    int mps, mp, n;
+    int sps, gs, ilv;       // strips per segment, groups per segment, interleave of the copy
+    int nsets;              // local segments x gs
+    int nsl, ntiles;        // 64-row slices; 128-row tile pairs I >= J
+    const double* w0;       // the point: prior, x', q - qbar, scalar slot (S_LOGS)
+    const double* x;
+    const double* qv;
+    const double* pscal;
+    double* partial;        // ForcesGramPlan's sets
+    size_t set_stride;
+    size_t rows_at;
+};
+
+__host__ __device__ inline int fgram16_sub(int si, int sj) { return si * (si + 1) / 2 + sj; }
+
+typedef __bf16 bfp __attribute__((ext_vector_type(2)));
+typedef float flp __attribute__((ext_vector_type(2)));
+
+// two floats -> two bfloat16 in one register (v0 in the low half), round to nearest even: v_cvt_pk_bf16_f32
+__device__ __forceinline__ unsigned bf_pack(float v0, float v1) {
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(flp{v0, v1}, bfp));
+}
+
+// v0, v1 = hi + lo + (what the split drops), both bfloat16: a register of two his and one of two los -- half a fragment
+__device__ __forceinline__ void bf_split2(double v0, double v1, unsigned& hi, unsigned& lo) {
+    const float f0 = (float)v0, f1 = (float)v1;
+    hi = bf_pack(f0, f1);
+    lo = bf_pack(f0 - __uint_as_float(hi << 16), f1 - __uint_as_float(hi & 0xffff0000u));       // exact in f32
+}
+
+__device__ __forceinline__ fl4 mfma16(u2v a, u2v b, fl4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(bh4, a), __builtin_bit_cast(bh4, b), c, 0, 0, 0);
+}
+
+struct FGram16Regs {
+    d2 a[kWaveRows / 8];
+    d2 b[kWaveRows / 8];
+    double w0, x, qv;                // the strip's column lane & 15: a lane forms the weights of ONE column, the others arrive by shuffles
+};
+
+__global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGram16Args q) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lq = lane >> 4, lr = lane & 15;
+    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+    const int set = (k / q.ntiles) * 8 + xcd;
+    if (set >= q.nsets) return;
+    int ti = 0, tj = k % q.ntiles;
+    while (tj > ti) tj -= ++ti;                     // tile pair (ti, tj), tj <= ti
+    const int si = 2 * ti + (wave >> 1), sj = 2 * tj + (wave & 1);
+    if (si >= q.nsl || sj > si) return;             // (no barrier in this kernel: a wave may leave)
+    const int v = set / q.gs, g = set - v * q.gs;
+    const int tg = (q.sps - g + q.gs - 1) / q.gs;   // strips of the set (g < gs <= sps: at least one)
+    const int ra = si * kWaveRows, rb = sj * kWaveRows;
+    int offa[kWaveRows / 8], offb[kWaveRows / 8];
+    strip_chunk_offsets(q.mps, ra, offa);
+    strip_chunk_offsets(q.mps, rb, offb);
+    const size_t wa = (size_t)ra * kStripCols + (size_t)lane * 2, wb = (size_t)rb * kStripCols + (size_t)lane * 2;
+    const double logs = q.pscal[S_LOGS];
+
+    double ca[4], cb[4];                            // the centres of the lane's rows
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        const int rowa = ra + 16 * h + lr, rowb = rb + 16 * h + lr;
+        ca[h] = rowa < q.mp ? q.center[rowa] : 0.0;
+        cb[h] = rowb < q.mp ? q.center[rowb] : 0.0;
+    }
+
+    auto fetch = [&](int i, FGram16Regs& r) {
+        const int s = v * q.sps + g + q.gs * i;
+        const double* src = q.Ys + (size_t)strip_phys(s, q.sps, q.ilv) * q.mps * kStripCols;
+#pragma unroll
+        for (int c = 0; c < kWaveRows / 8; ++c) r.a[c] = ldg2<false>(src + wa + offa[c]);
+#pragma unroll
+        for (int c = 0; c < kWaveRows / 8; ++c) r.b[c] = ldg2<false>(src + wb + offb[c]);
+        const size_t col = (size_t)s * kStripCols + lr;
+        r.w0 = q.w0[col];
+        r.x = q.x[col];
+        r.qv = q.qv[col];
+    };
+
+    fl4 acc1[4][4], acc2[4][4];                     // [row block of slice si][row block of slice sj]
+    double rs[4];                                   // the lane's share of the row sums of Y' u2 (slice si)
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        rs[h] = 0.0;
+#pragma unroll
+        for (int gb = 0; gb < 4; ++gb) {
+            acc1[h][gb] = fl4{0.f, 0.f, 0.f, 0.f};
+            acc2[h][gb] = fl4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+
+    // One register set, as in k_forces_gram: a strip's operands are centred, weighted and split into registers of their own
+    // as soon as it has arrived, the set is refilled with the NEXT strip, which travels while this one is multiplied.
+    FGram16Regs pre;
+    fetch(0, pre);
+#pragma unroll 1
+    for (int i = 0; i < tg; ++i) {
+        // the point's weights as k_forces_gram forms them (the same operations, so the same bits), columns beyond n weigh
+        // nothing -- formed once per column (lane & 15) and handed to the lanes that multiply with them: 4 qq + lq
+        const size_t colc = (size_t)(v * q.sps + g + q.gs * i) * kStripCols + lr;
+        const double e = exp(pre.x - logs);
+        const double u1c = colc < (size_t)q.n ? pre.w0 * e : 0.0;
+        const double u2c = u1c * pre.qv;
+        double u1[4], u2[4];
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) {
+            u1[qq] = __shfl(u1c, 4 * qq + lq, 64);
+            u2[qq] = __shfl(u2c, 4 * qq + lq, 64);
+        }
+        u2v ah[4], al[4], b1h[4], b1l[4], b2h[4], b2l[4];       // [row block]: the fragments, element qq = column quad qq
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+#pragma unroll
+            for (int qp = 0; qp < 2; ++qp) {                    // the column quads 2 qp (.x) and 2 qp + 1 (.y)
+                const d2 av = pre.a[2 * h + qp], bv = pre.b[2 * h + qp];
+                const double a0 = av.x - ca[h], a1 = av.y - ca[h];
+                const double b0 = bv.x - cb[h], b1 = bv.y - cb[h];
+                rs[h] = fma(a0, u2[2 * qp], rs[h]);
+                rs[h] = fma(a1, u2[2 * qp + 1], rs[h]);
+                unsigned hi, lo;
+                bf_split2(a0, a1, hi, lo);
+                ah[h][qp] = hi;
+                al[h][qp] = lo;
+                bf_split2(b0 * u1[2 * qp], b1 * u1[2 * qp + 1], hi, lo);
+                b1h[h][qp] = hi;
+                b1l[h][qp] = lo;
+                bf_split2(b0 * u2[2 * qp], b1 * u2[2 * qp + 1], hi, lo);
+                b2h[h][qp] = hi;
+                b2l[h][qp] = lo;
+            }
+        fetch(i + 1 < tg ? i + 1 : i, pre);         // unconditional
+        asm volatile("" ::: "memory");              // the loads are issued HERE, in front of the products
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+#pragma unroll
+            for (int gb = 0; gb < 4; ++gb) {
+                acc1[h][gb] = mfma16(ah[h], b1h[gb], acc1[h][gb]);
+                acc2[h][gb] = mfma16(ah[h], b2h[gb], acc2[h][gb]);
+                acc1[h][gb] = mfma16(ah[h], b1l[gb], acc1[h][gb]);
+                acc2[h][gb] = mfma16(ah[h], b2l[gb], acc2[h][gb]);
+                acc1[h][gb] = mfma16(al[h], b1h[gb], acc1[h][gb]);
+                acc2[h][gb] = mfma16(al[h], b2h[gb], acc2[h][gb]);
+            }
+    }
+
+    // The set leaves as doubles on k_forces_gram's layout (fgram_elem: element (i, j) of a 16 x 16 block at register
+    // (i & 15) >> 2 of lane 16 (i & 3) + j).  Result register r of lane 16 lq + lr of THIS instruction is row 4 lq + r,
+    // column lr of the block: it goes to register slot lq, lane 16 r + lr.  Row blocks beyond the strip's last one were
+    // redirected (strip_chunk_offsets): what they leave lies beyond row m and is never read (k_fgram_finish).
+    double* const dst = q.partial + (size_t)set * q.set_stride + (size_t)fgram16_sub(si, sj) * kFGram16SubDoubles + lr;
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+        for (int gb = 0; gb < 4; ++gb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                dst[((0 * 16 + h * 4 + gb) * 4 + lq) * 64 + 16 * r] = (double)acc1[h][gb][r];
+                dst[((1 * 16 + h * 4 + gb) * 4 + lq) * 64 + 16 * r] = (double)acc2[h][gb][r];
+            }
+    if (sj == 0) {                                  // (wave-uniform) the slices' row sums: one writer per slice and set
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            double t = rs[h];
+            t += __shfl_xor(t, 16, 64);
+            t += __shfl_xor(t, 32, 64);
+            const int row = ra + 16 * h + lr;
+            if (lq == 0) q.partial[(size_t)set * q.set_stride + q.rows_at + row] = row < q.mps ? t : 0.0;
+        }
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------
+// buf: forces_gram_plan's doubles (a buffer of this entry's own); x, pscal, qv, ybar: the kept point's.  Leaves C~ at
+// buf + cov_at, H~ at buf + hess_at.
+void launch_forces_gram_bf16(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
+                             const double* qv, const double* ybar, double theta) {
+    FGram16Args q{};
+    q.Ys = c->Ys[0];
+    q.center = c->strip_center;
+    q.mps = panel_mps(c, 0);
+    q.mp = c->mp;
+    q.n = c->n;
+    q.sps = strip_sps(c);
+    q.gs = p.gs;
+    q.ilv = strip_ilv(c);
+    q.nsets = p.nsets;
+    q.nsl = p.nsl;
+    q.ntiles = p.ntiles;
+    q.w0 = c->fixed;
+    q.x = x;
+    q.qv = qv;
+    q.pscal = pscal;
+    q.partial = buf;
+    q.set_stride = p.set_stride;
+    q.rows_at = p.rows_at;
+    const int nblk = 8 * p.ntiles * ((p.nsets + 7) / 8);
+    hipLaunchKernelGGL(k_forces_gram_bf16, dim3(nblk), dim3(256), 0, c->stream, q);
+    double* sum = buf + (size_t)p.nsets * p.set_stride;
+    const int sum_blocks = (int)std::min<size_t>((p.set_stride + kBlock - 1) / kBlock, 4096);
+    hipLaunchKernelGGL(k_fgram_sum_sets, dim3(sum_blocks), dim3(kBlock), 0, c->stream, buf, p.set_stride, p.set_stride, c->vr,
+                       p.gs, sum);
+    const int tb = (c->m + 15) / 16;
+    hipLaunchKernelGGL(k_fgram_finish, dim3(tb, tb), dim3(256), 0, c->stream, sum, p.rows_at, c->m, theta, ybar, c->row_scale,
+                       c->affine, buf + p.cov_at, buf + p.hess_at);
+    hipLaunchKernelGGL(k_fgram_square, dim3(tb, tb), dim3(256), 0, c->stream, buf + p.cov_at, c->m, buf + p.hess_at);
+}
+
+}  // namespace bioen

@@ -185,6 +185,63 @@ def hessian_gram_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta, use
     return C, 0.5 * (H + H.T)
 
 
+def _bf16_round(v):
+    """float32 array -> the nearest bfloat16 (ties to even) as float32, by integer arithmetic on the bit pattern"""
+    u = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+    u = (u + np.uint32(0x7fff) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xffff0000)
+    return u.view(np.float32)
+
+
+def _bf16_split(v):
+    """FP64 array -> (hi, lo) as FP64 arrays holding bfloat16 numbers: hi = bf((float)v), lo = bf((float)v - hi) -- the
+    subtraction is exact in float32"""
+    f = np.asarray(v, dtype=np.float64).astype(np.float32)
+    hi = _bf16_round(f)
+    lo = _bf16_round(f - hi)
+    return hi.astype(np.float64), lo.astype(np.float64)
+
+
+def hessian_gram_bf16_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta, use_c=True):
+    """(C~, H~), both (m, m): the numpy restatement of Context.forces_gram_bf16 -- the covariance and the dense
+    Hessian of hessian_gram_bioen_log_posterior_base with the two M x M x N products formed from split-BF16 operands, as
+    a Newton minimizer's Hessian (good to about 1e-5 ... 1e-4 of max|H|).  With Y' = yTilde - YTilde (the device's centre),
+    u1 = w, u2 = w (q - <q>) and bf(v) = round-to-nearest-even of (float)v to bfloat16:
+
+      a = Y'_ij (FP64)         a_hi = bf(a),  a_lo = bf((float)a - a_hi)
+      t = a u_j (FP64)         t_hi = bf(t),  t_lo = bf((float)t - t_hi)
+      G'[u] = sum_j (a_hi t_hi + a_hi t_lo + a_lo t_hi)         each product exact in FP64, summed in FP64
+      g = sum_j u2_j Y'_j,  ybar' = ybar - YTilde               FP64
+      C~ = G'[u1] - ybar' ybar'^T,   G2 = G'[u2] - g ybar'^T - ybar' g^T,   H~ = theta C~ + G2 + C~ C~
+
+    The lower triangle is computed and mirrored: both results are symmetric bit for bit."""
+    yT = np.asarray(yTilde, dtype=np.float64)
+    f = np.asarray(forces, dtype=np.float64).reshape(-1)
+    w = get_weights_from_forces(w0, yT, f)[:, 0]
+    centre = np.asarray(YTilde, dtype=np.float64).reshape(-1)
+    ybar = yT.dot(w)
+    x = yT.T.dot(f)
+    q = theta * (x - w.dot(x)) + yT.T.dot(ybar - centre)
+    q -= w.dot(q)
+    a = yT - centre[:, None]
+    a_hi, a_lo = _bf16_split(a)
+
+    def gram(u):
+        t_hi, t_lo = _bf16_split(a * u[None, :])
+        return a_hi.dot(t_hi.T) + a_hi.dot(t_lo.T) + a_lo.dot(t_hi.T)
+
+    u2 = w * q
+    yc = a.dot(w)                        # ybar' = ybar - centre, formed from the centred operand
+    g = a.dot(u2)
+    C = gram(w) - np.outer(yc, yc)
+    G2 = gram(u2) - np.outer(g, yc) - np.outer(yc, g)
+    T = theta * C + G2
+    C = np.tril(C) + np.tril(C, -1).T
+    T = np.tril(T) + np.tril(T, -1).T
+    S = C.dot(C)
+    H = T + (np.tril(S) + np.tril(S, -1).T)
+    return C, H
+
+
 def hessp_bioen_log_posterior(forces, p, w0, y, yTilde, YTilde, theta, use_c=True, caching=False):
     """Hessian-vector product w.r.t. the m forces; `y` unused."""
     if use_c:
@@ -279,23 +336,30 @@ _SCIPY_DENSE = {"trust_exact": "trust-region Newton, exact subproblem", "trust-e
 
 
 # scipy:hessian -- where trust-exact's dense Hessian comes from: "products" (the default: ceil(m / 8) batched products at
-# the kept point, Context.forces_hessian) or "gram" (one compute-bound pass, Context.forces_gram; M <= 1024)
-_HESSIAN_SOURCES = ("products", "gram")
+# the kept point, Context.forces_hessian), "gram" (one compute-bound pass on the FP64 matrix cores, Context.forces_gram;
+# M <= 1024) or "gram_bf16" (the same pass from split-BF16 operands, Context.forces_gram_bf16: a minimizer's Hessian, good
+# to 1e-5 ... 1e-4 of max|H|; the gradient stays FP64, so the minimum is the same, but the last steps converge linearly, not
+# quadratically: with a large theta or a tight gtol scipy may end with status 2 just above gtol -- DESIGN 6g)
+_HESSIAN_SOURCES = ("products", "gram", "gram_bf16")
 
 
 def _hessian_source(cfg):
-    """the scipy parameter `hessian`, checked: -> "products" | "gram" """
+    """the scipy parameter `hessian`, checked: -> "products" | "gram" | "gram_bf16" """
     source = str(cfg["params"].get("hessian", "products")).lower()
     if source not in _HESSIAN_SOURCES:
-        raise RuntimeError("scipy:hessian=" + source + " not recognized (valid values = 'products', 'gram')")
-    if source == "gram" and str(cfg["algorithm"]).lower() not in _SCIPY_DENSE:
-        raise RuntimeError("scipy:hessian=gram serves scipy:algorithm=trust_exact only (the other drivers take no dense "
+        raise RuntimeError("scipy:hessian=" + source + " not recognized (valid values = 'products', 'gram', 'gram_bf16')")
+    if source != "products" and str(cfg["algorithm"]).lower() not in _SCIPY_DENSE:
+        raise RuntimeError("scipy:hessian=" + source + " serves scipy:algorithm=trust_exact only (the other drivers take no dense "
                            "Hessian); got algorithm " + str(cfg["algorithm"]))
     return source
 
 
 def _hess_gram_base(forces, w0, yTilde, YTilde, theta):
     return hessian_gram_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta)[1]
+
+
+def _hess_gram_bf16_base(forces, w0, yTilde, YTilde, theta):
+    return hessian_gram_bf16_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta)[1]
 
 
 def _run_scipy_trust_exact(cfg, f, fprime, hess, x0, args):
@@ -315,7 +379,7 @@ class _DeviceFdf(object):
     def __init__(self, w0, yTilde, YTilde, theta, keep_point=False, hessian="products"):
         self.ctx, self._cached = c_bioen._context_for(yTilde, YTilde)
         self._keep_point = keep_point       # trust-exact: every evaluation leaves the point for the products at it
-        self._hessian = hessian             # "gram": the dense Hessian from Context.forces_gram
+        self._hessian = hessian             # "gram" / "gram_bf16": the dense Hessian from Context.forces_gram / forces_gram_bf16
         self.w0 = np.asarray(w0, dtype=np.float64).reshape(-1)
         self.theta = theta
         self._x = None
@@ -345,10 +409,13 @@ class _DeviceFdf(object):
         return self.ctx.forces_hessp(np.asarray(p, dtype=np.float64).reshape(-1))
 
     def hess(self, x, *unused):
-        """the dense Hessian at x: ceil(m / 8) batched products at the kept point, or (scipy:hessian=gram) one Gram pass"""
+        """the dense Hessian at x: ceil(m / 8) batched products at the kept point, or (scipy:hessian=gram, gram_bf16) one
+        Gram pass"""
         self._set_point(x)
         if self._hessian == "gram":
             return self.ctx.forces_gram(cov=False)[1]
+        if self._hessian == "gram_bf16":
+            return self.ctx.forces_gram_bf16(cov=False)[1]
         return self.ctx.forces_hessian()
 
     def f(self, x, *unused):
@@ -432,7 +499,8 @@ def _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
         common.print_highlighted("FORCES -- Library scipy/PY", cfg["verbose"])
         if dense:
             res = _run_scipy_trust_exact(cfg, bioen_log_posterior_base, grad_bioen_log_posterior_base,
-                                         _hess_gram_base if hessian == "gram" else hessian_bioen_log_posterior_base,
+                                         {"gram": _hess_gram_base, "gram_bf16": _hess_gram_bf16_base}.get(
+                                             hessian, hessian_bioen_log_posterior_base),
                                          forces, (w0, yTilde, YTilde, theta))
         else:
             res = _run_scipy(cfg, bioen_log_posterior_base, grad_bioen_log_posterior_base, forces,

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """What the dense Hessian of the forces objective costs in ONE compute-bound pass (Context.forces_gram) next to the method
 it replaces, ceil(M / 8) batched products at the same kept point (Context.forces_hessian), in ONE process: wall time per
-call, each ending synchronised, the two call shapes alternating.  Condition: forces_gram(cov, hess) takes
-at most 0.5 x forces_hessian() at 512 x 1e6 and 1024 x 1e5.
+call, each ending synchronised, the call shapes alternating -- and, as a third leg, the same pass from split-BF16 operands
+(Context.forces_gram_bf16) with one forces_fdf evaluation, the memory floor, as a fourth.  Conditions:
+forces_gram(cov, hess) takes at most 0.5 x forces_hessian() and forces_gram_bf16 at most 0.5 x forces_gram
+(by kernel time: a --once run under a kernel trace) at 512 x 1e6 and 1024 x 1e5.
 
     python3 tools/forces_gram_probe.py [M] [N] [reps]                # GPU box; default 512 x 1e6, 5 repetitions
-    python3 tools/forces_gram_probe.py --once [M] [N] [calls]        # point set, then forces_gram `calls` times (default 2): for a counter or kernel-trace run
-    python3 tools/forces_gram_probe.py --minimizer [M] [N] [theta]   # trust-exact with hessian = gram / products (driven as
+    python3 tools/forces_gram_probe.py --once [M] [N] [calls]        # point set, then forces_gram and forces_gram_bf16 alternately, `calls` times each (default 2): for a counter or kernel-trace run
+    python3 tools/forces_gram_probe.py --minimizer [M] [N] [theta]   # trust-exact with hessian = gram_bf16 / gram / products (--skip-products: without the last; driven as
                                         # find_optimum drives it), cold start, against the converged device L-BFGS on one
                                         # seeded problem (default 256 x 1e5, theta 10)
 """
@@ -47,10 +49,13 @@ def timing(M, N, reps):
     with bioen_amd.Context.synthetic(M, N, YTrue, sig_sim, sig_exp, YTilde, seed=12345) as ctx:
         ctx.forces_hessp(None, forces=f, w0=w0, theta=theta)
         shapes = {"forces_hessian_products": lambda: ctx.forces_hessian(),
-                  "forces_gram_cov_hess": lambda: ctx.forces_gram()}
+                  "forces_gram_cov_hess": lambda: ctx.forces_gram(),
+                  "forces_gram_bf16_cov_hess": lambda: ctx.forces_gram_bf16(),
+                  "forces_hessp_point_only": lambda: ctx.forces_hessp(None, forces=f, w0=w0, theta=theta)}   # = one forces_fdf
         order = list(shapes)
-        Hp = shapes[order[0]]()                              # warm-up of both call shapes (work vectors, the sets' buffer)
+        Hp = shapes[order[0]]()                              # warm-up of the call shapes (work vectors, the sets' buffers)
         C, H = shapes[order[1]]()
+        Cb, Hb = shapes[order[2]]()
         ctx.synchronize()
         times = {name: [] for name in order}
         for _ in range(reps):                                # alternating
@@ -62,6 +67,10 @@ def timing(M, N, reps):
         out["wall"] = {name: stats(times[name]) for name in order}
         out["ratio_gram_to_products"] = round(out["wall"][order[1]]["mean_ms"] / out["wall"][order[0]]["mean_ms"], 4)
         out["condition_at_most_0.5"] = bool(out["ratio_gram_to_products"] <= 0.5)
+        out["ratio_gram_bf16_to_gram"] = round(out["wall"][order[2]]["mean_ms"] / out["wall"][order[1]]["mean_ms"], 4)
+        out["ratio_gram_bf16_to_one_evaluation"] = round(out["wall"][order[2]]["mean_ms"] / out["wall"][order[3]]["mean_ms"], 4)
+        out["bf16_max_dH_over_max_H"] = float(np.abs(Hb - H).max() / np.abs(H).max())
+        out["bf16_max_dC_over_max_C"] = float(np.abs(Cb - C).max() / np.abs(C).max())
         # the flops the pass performs: two M x M x N products on the lower triangle's 64 x 64 sub-tiles; of the floor 2 . 2 M^2 N
         nsl = -(-M // 64)
         done = 2 * 2 * (nsl * (nsl + 1) // 2) * 64 * 64 * float(N)
@@ -81,9 +90,10 @@ def once(M, N, calls=2):
     f = 1e-3 * rng.standard_normal(M)
     with bioen_amd.Context.synthetic(M, N, YTrue, sig_sim, sig_exp, YTilde, seed=12345) as ctx:
         ctx.forces_hessp(None, forces=f, w0=w0, theta=10.0)
-        for _ in range(calls):
+        for _ in range(calls):                               # the two kernels alternately, from one process
             ctx.forces_gram()
-    return {"M": M, "N": N, "forces_gram_calls": calls}
+            ctx.forces_gram_bf16()
+    return {"M": M, "N": N, "forces_gram_calls": calls, "forces_gram_bf16_calls": calls}
 
 
 def minimizer_record(M, N, theta):
@@ -101,12 +111,14 @@ def minimizer_record(M, N, theta):
         fl, wl, info = ctx.opt_lbfgs_forces(x0, w0, theta, conv)
         out["lbfgs_converged"] = {"seconds": round(time.perf_counter() - t0, 3), "iterations": info.iterations,
                                   "evaluations": info.evaluations, "code": info.lbfgs_code, "fmin": info.fmin}
-        for source in ("gram", "products"):
-            state = {"x": None, "f": None, "g": None, "evals": 0, "hessians": 0}
+        for source in ("gram_bf16", "gram") + (() if "--skip-products" in flags else ("products",)):
+            state = {"x": None, "f": None, "g": None, "evals": 0, "hessians": 0, "device_s": 0.0}
 
             def ev(x):                                       # as _DeviceFdf under trust-exact: every evaluation sets the point
                 if state["x"] is None or not np.array_equal(x, state["x"]):
+                    t = time.perf_counter()
                     _, state["f"], state["g"] = ctx.forces_hessp(None, forces=x, w0=w0, theta=theta)
+                    state["device_s"] += time.perf_counter() - t
                     state["x"] = x.copy()
                     state["evals"] += 1
 
@@ -121,10 +133,16 @@ def minimizer_record(M, N, theta):
             def hess(x):
                 ev(x)
                 state["hessians"] += 1
-                return ctx.forces_gram(cov=False)[1] if source == "gram" else ctx.forces_hessian()
+                t = time.perf_counter()
+                try:
+                    if source == "gram_bf16":
+                        return ctx.forces_gram_bf16(cov=False)[1]
+                    return ctx.forces_gram(cov=False)[1] if source == "gram" else ctx.forces_hessian()
+                finally:
+                    state["device_s"] += time.perf_counter() - t
 
             hess(x0)                                         # warm-up (the sets' buffer, the directions' work vectors)
-            state.update(x=None, evals=0, hessians=0)
+            state.update(x=None, evals=0, hessians=0, device_s=0.0)
             t0 = time.perf_counter()
             try:
                 with warnings.catch_warnings():
@@ -136,13 +154,16 @@ def minimizer_record(M, N, theta):
                 continue
             dt = time.perf_counter() - t0
             wn = ctx.forces_weights(res.x, w0)
-            out["trust_exact_" + source] = {"seconds": round(dt, 3), "iterations": int(res.nit), "evaluations": state["evals"],
+            out["trust_exact_" + source] = {"seconds": round(dt, 3), "seconds_in_device_calls": round(state["device_s"], 3),
+                                            "seconds_in_scipy_on_the_host": round(dt - state["device_s"], 3), "iterations": int(res.nit), "evaluations": state["evals"],
                                             "hessians": state["hessians"], "success": bool(res.success),
                                             "status": int(res.status), "message": str(res.message), "fmin": float(res.fun),
                                             "max_abs_grad": float(np.abs(res.jac).max()),
                                             "dfmin_vs_lbfgs": float(res.fun - info.fmin),
                                             "max_dw_over_max_w": float(np.abs(wn - wl).max() / wl.max())}
-        if "fmin" in out["trust_exact_gram"] and "fmin" in out["trust_exact_products"]:
+        if "fmin" in out["trust_exact_gram"] and "fmin" in out["trust_exact_gram_bf16"]:
+            out["dfmin_gram_bf16_vs_gram"] = out["trust_exact_gram_bf16"]["fmin"] - out["trust_exact_gram"]["fmin"]
+        if "fmin" in out["trust_exact_gram"] and "fmin" in out.get("trust_exact_products", {}):
             out["dfmin_gram_vs_products"] = out["trust_exact_gram"]["fmin"] - out["trust_exact_products"]["fmin"]
     return out
 
