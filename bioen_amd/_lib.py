@@ -493,7 +493,11 @@ class Context(object):
         """The regime of the strip passes' launch plan (bioen_hip_ctx_strip_plan; no device call).  which: 0 = the
         log-weights forward pass, 1 = the forces passes.  -> {"sps": strips per segment, "gs": groups per segment (0: the
         strip passes do not apply), "tc": strips per chunk (forces: the most strips a group runs per segment), "nch": chunks
-        per group, "fold": a slot runs a whole group, "local_segments"}"""
+        per group, "fold": a slot runs a whole group, "local_segments"}
+        which = 2: the streaming pair on the row-major matrix (what serves a context without strip copies; answered whether
+        or not the context is on it -- pair it with footprint() == {"rowmajor"} after the first evaluation): "sps": 128-column
+        steps per segment, "gs": column tiles per segment, "tc": steps per tile, "nch": rows a wave of the adjoint kernel
+        walks, "fold": 1 = non-temporal matrix loads, "local_segments"."""
         o = [C.c_int(0) for _ in range(6)]
         check(lib().bioen_hip_ctx_strip_plan(self._h, int(which), *[C.byref(v) for v in o]))
         return dict(zip(("sps", "gs", "tc", "nch", "fold", "local_segments"), (v.value for v in o)))

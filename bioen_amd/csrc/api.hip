@@ -1212,7 +1212,17 @@ int bioen_hip_ctx_layout(const bioen_hip_ctx* c, int* one_copy, int* interleave,
 int bioen_hip_ctx_strip_plan(const bioen_hip_ctx* c, int pass, int* sps, int* gs, int* tc, int* nch, int* fold,
                              int* local_segments) {
     if (int rc = enter(c, FX_NONE, __func__)) return rc;
-    if (pass != 0 && pass != 1) return fail(BIOEN_HIP_EINVAL, "bioen_hip_ctx_strip_plan: pass is 0 (log-weights forward) or 1 (forces)");
+    if (pass < 0 || pass > 2)
+        return fail(BIOEN_HIP_EINVAL, "bioen_hip_ctx_strip_plan: pass is 0 (log-weights forward), 1 (forces) or 2 (the streaming pair)");
+    if (pass == 2) {       // the streaming pair on the row-major matrix: the context fields its launchers pass (kernels_matrix.hip)
+        if (sps) *sps = c->segcols / 128;
+        if (gs) *gs = c->fwd_ctiles / c->vr;
+        if (tc) *tc = c->fwd_steps;
+        if (nch) *nch = adj_rows_per_wave(c);
+        if (fold) *fold = c->nontemporal ? 1 : 0;
+        if (local_segments) *local_segments = c->vr;
+        return 0;
+    }
     const StripSets ss = pass == 0 ? strip_sets(c) : forces_sets(c);      // what the launchers take (strip_plan.cpp)
     if (sps) *sps = ss.sps;
     if (gs) *gs = ss.gs;

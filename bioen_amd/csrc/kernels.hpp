@@ -57,6 +57,7 @@ struct SegMap {                         // what an N-vector kernel without a sta
 SegMap seg_map(const bioen_hip_ctx* c);
 void rank_columns(const bioen_hip_ctx* c, int rank, long long* col0, long long* n_local);   // columns of `rank` in this context's decomposition
 int rows_grid(const bioen_hip_ctx* c);
+int adj_rows_per_wave(const bioen_hip_ctx* c);   // rows a wave of k_adj walks (what launch_adj passes; bioen_hip_ctx_strip_plan reports it)
 
 // ---- matrix streaming kernels ------------------------------------------------
 // forward: fwd_partial[(row*K + a)*ctiles + tile] = sum_{j in tile} (Y[row][j] - [centred] ybar_c[row*K+a]) v_a[j]

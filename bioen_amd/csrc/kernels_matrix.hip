@@ -546,7 +546,7 @@ int rows_grid(const bioen_hip_ctx* c) {
     return b;
 }
 
-
+int adj_rows_per_wave(const bioen_hip_ctx* c) { return c->mp / kWaves; }
 
 // ---- forward ---------------------------------------------------------------------------
 template <int K, int STEPS, bool NT, bool CENTER>
@@ -695,7 +695,7 @@ template <int K, bool NT, bool CENTER>
 static void adj_launch(bioen_hip_ctx* c, const double* u_c, const MVec8& out) {
     dim3 grid((unsigned)(c->ld / 128));
     BIOEN_LAUNCH_TIMED(c, (k_adj<8, K, NT, CENTER, (K >= 4 && K <= 7)>), grid, dim3(kBlock), 0, c->Y, c->ld,
-                       c->mp / kWaves, u_c, c->ybar_c, out);
+                       adj_rows_per_wave(c), u_c, c->ybar_c, out);
 }
 
 template <bool NT, bool CENTER>

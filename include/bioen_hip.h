@@ -187,8 +187,13 @@ int bioen_hip_ctx_layout(const bioen_hip_ctx* ctx, int* one_copy, int* interleav
  * Per column segment: its sps strips of 16 columns are dealt to gs groups (group g: strips g, g + gs, ...), so the
  * first sps - gs * (ceil(sps / gs) - 1) groups hold ceil(sps / gs) strips and the others one fewer.  tc: strips per chunk (forces passes: per
  * group and segment, the larger count), nch: chunks per group, fold: 1 = a slot runs a whole group and adds its chunks up
- * in registers, local_segments: the segments this context holds.  Any result pointer may be NULL; another pass is
- * BIOEN_HIP_EINVAL.  For tests that must prove a slot ran several strips of a segment. */
+ * in registers, local_segments: the segments this context holds.
+ * pass 2: the streaming pair on the row-major matrix (k_fwd_partial / k_adj: what serves a context without strip copies),
+ * whether or not the context is on it at the moment -- sps: 128-column steps per segment, gs: column tiles per segment, tc:
+ * steps per tile (a segment's last tile is cut at the segment's end), nch: rows a wave of the adjoint kernel walks, fold:
+ * 1 = the passes use non-temporal loads, local_segments as above.
+ * Any result pointer may be NULL; another pass is BIOEN_HIP_EINVAL.  For tests that must prove a slot ran several strips
+ * of a segment, or a tile several steps. */
 int bioen_hip_ctx_strip_plan(const bioen_hip_ctx* ctx, int pass, int* sps, int* gs, int* tc, int* nch, int* fold,
                              int* local_segments);
 /* r05: ask for (1) / give up (0) the ONE-copy form described above; to be called before the context's first gradient
