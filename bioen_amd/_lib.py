@@ -43,6 +43,26 @@ class OptResult(C.Structure):
                 ("evaluations", C.c_int), ("reserved", C.c_int)]
 
 
+class NewtonConfig(C.Structure):
+    # bioen_newton_config (include/bioen_hip_forces_newton.h)
+    _fields_ = [("gtol", C.c_double), ("armijo", C.c_double), ("rho_good", C.c_double), ("lambda_factor", C.c_double),
+                ("lambda_first", C.c_double), ("lambda_max", C.c_double), ("lambda_zero", C.c_double),
+                ("floor_ulps", C.c_double), ("max_iterations", C.c_int), ("hessian", C.c_int)]
+
+
+class NewtonResult(C.Structure):
+    # bioen_newton_result (include/bioen_hip_forces_newton.h)
+    _fields_ = [("fmin", C.c_double), ("gmax", C.c_double), ("lam", C.c_double), ("status", C.c_int),
+                ("iterations", C.c_int), ("evaluations", C.c_int), ("hessians", C.c_int), ("factorisations", C.c_int),
+                ("switched", C.c_int)]
+
+
+# the Newton minimizer's damping constants (forces.newton_bioen_log_posterior_base uses the same)
+NEWTON_DEFAULTS = dict(gtol=1e-6, max_iterations=200, hessian="gram", armijo=1e-4, rho_good=0.75, lambda_factor=4.0,
+                       lambda_first=1e-10, lambda_max=1e10, lambda_zero=1e-12, floor_ulps=8.0)
+NEWTON_SOURCES = ("gram", "gram_bf16")
+
+
 class BioenHipError(RuntimeError):
     """Failure inside libbioen_hip (HIP runtime, allocation, bad argument)."""
 
@@ -162,6 +182,15 @@ _SIGNATURES_FORCES_GRAM_BF16 = {
     "bioen_hip_forces_gram_bf16": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp]),
 }
 
+# every symbol include/bioen_hip_forces_newton.h declares (the sixth public header: the device-resident Newton minimizer
+# of the forces method, its Cholesky factorisation and solves); bound by lib() beside the other five
+_SIGNATURES_FORCES_NEWTON = {
+    "bioen_hip_forces_newton_factor": (C.c_int, [ctx_p, dp, C.c_int, C.c_double, dp, C.POINTER(C.c_int)]),
+    "bioen_hip_forces_newton_solve": (C.c_int, [ctx_p, C.c_int, dp, dp]),
+    "bioen_hip_opt_newton_forces": (C.c_int, [ctx_p, dp, dp, C.c_double, C.POINTER(NewtonConfig), dp, dp,
+                                              C.POINTER(NewtonResult)]),
+}
+
 _lib = None
 
 
@@ -185,6 +214,10 @@ def exported_symbols_forces_gram_bf16():
     return sorted(_SIGNATURES_FORCES_GRAM_BF16)
 
 
+def exported_symbols_forces_newton():
+    return sorted(_SIGNATURES_FORCES_NEWTON)
+
+
 def lib():
     """Load libbioen_hip.so (once).  Raises if it has not been built."""
     global _lib
@@ -196,7 +229,7 @@ def lib():
                 "There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP, _SIGNATURES_FORCES_GRAM, _SIGNATURES_FORCES_COLQUAD,
-                      _SIGNATURES_FORCES_GRAM_BF16):
+                      _SIGNATURES_FORCES_GRAM_BF16, _SIGNATURES_FORCES_NEWTON):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)          # AttributeError here = header/library mismatch
                 fn.restype = res
@@ -261,6 +294,22 @@ def as_f64(x, shape=None):
 
 def ptr(a):
     return a.ctypes.data_as(dp)
+
+
+def newton_source(value):
+    """the Newton minimizer's Hessian source, checked: "gram" | "gram_bf16" -> 0 | 1"""
+    v = str(value).lower()
+    if v not in NEWTON_SOURCES:
+        raise RuntimeError("newton:hessian=" + v + " not recognized (valid values = 'gram', 'gram_bf16')")
+    return NEWTON_SOURCES.index(v)
+
+
+def newton_config(params):
+    """params (a dict; missing keys take NEWTON_DEFAULTS) -> NewtonConfig"""
+    p = dict(NEWTON_DEFAULTS, **(params or {}))
+    return NewtonConfig(float(p["gtol"]), float(p["armijo"]), float(p["rho_good"]), float(p["lambda_factor"]),
+                        float(p["lambda_first"]), float(p["lambda_max"]), float(p["lambda_zero"]), float(p["floor_ulps"]),
+                        int(p["max_iterations"]), newton_source(p["hessian"]))
 
 
 def lbfgs_config(params):
@@ -474,12 +523,13 @@ class Context(object):
     def footprint(self):
         """(forms, bytes) of the resident copies of the matrix: forms is a set out of {"rowmajor", "strips", "strips_colsum"};
         plus "bfgs_hinv" and its N x N bytes while a BFGS session (bfgs_logw) is live, and "forces_gram", the device buffer
-        of forces_gram, "forces_colquad", the one of forces_colquad, and "forces_gram_bf16", the one of forces_gram_bf16, each from its first
+        of forces_gram, "forces_colquad", the one of forces_colquad, "forces_gram_bf16", the one of forces_gram_bf16, and
+        "forces_newton", the factor L and the work buffers of forces_newton_factor / opt_newton_forces, each from its first
         call on"""
         f, b = C.c_int(0), C.c_longlong(0)
         check(lib().bioen_hip_ctx_footprint(self._h, C.byref(f), C.byref(b)))
         names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced", 16: "bfgs_hinv", 32: "forces_gram",
-                 64: "forces_colquad", 128: "forces_gram_bf16"}
+                 64: "forces_colquad", 128: "forces_gram_bf16", 256: "forces_newton"}
         return {names[k] for k in names if f.value & k}, b.value
 
     def layout(self):
@@ -846,6 +896,57 @@ class Context(object):
         grad = np.empty(m)
         check(fn(self._h, ptr(fo), ptr(w0), float(theta), pc, ph, C.byref(f), ptr(grad)))
         return C_, H, f.value, grad
+
+    def forces_newton_factor(self, A=None, source="gram", lam=0.0, want_L=True):
+        """(L or None, info): the FP64 Cholesky factorisation A + lam I = L L^T on the device (M <= 1024).  A: an
+        (m, m) matrix of which only the lower triangle is read; A=None: the Hessian of the kept forces point from `source`
+        ("gram": forces_gram's H, "gram_bf16": forces_gram_bf16's), computed now and not downloaded.  info is LAPACK
+        dpotrf's: 0, or k + 1 where pivot k was <= 0 or not finite (an ordinary result: L is None then and
+        forces_newton_solve is refused until a factorisation succeeds).  The same bits in give the same bits out.  Keeps
+        point and session; the first call allocates a device buffer that stays with the context (footprint():
+        "forces_newton")."""
+        m = self.m
+        pa = None
+        if A is not None:
+            A = as_f64(A)
+            if A.shape != (m, m):
+                raise ValueError("A must have shape (%d, %d)" % (m, m))
+            pa = ptr(A)
+        L = np.zeros((m, m)) if want_L else None
+        info = C.c_int(0)
+        check(lib().bioen_hip_forces_newton_factor(self._h, pa, 0 if A is not None else newton_source(source), float(lam),
+                                                   ptr(L) if want_L else None, C.byref(info)))
+        return (L if info.value == 0 else None), info.value
+
+    def forces_newton_solve(self, B):
+        """X = (L L^T)^-1 B with the factor of the last forces_newton_factor call; B: (m,) or (k, m), k <= 8 right-hand
+        sides as rows.  A row's result does not depend on k."""
+        B = as_f64(B)
+        one = B.ndim == 1
+        B2 = np.ascontiguousarray(B.reshape(1, -1) if one else B)
+        if B2.ndim != 2 or B2.shape[1] != self.m:
+            raise ValueError("B must have shape (m,) or (k, m)")
+        X = np.empty_like(B2)
+        check(lib().bioen_hip_forces_newton_solve(self._h, int(B2.shape[0]), ptr(B2), ptr(X)))
+        return X[0] if one else X
+
+    def opt_newton_forces(self, forces0, w0, theta, params=None, want_weights=True):
+        """Regularised Newton on the forces objective, the loop on the device side of the C ABI: H from
+        params["hessian"] ("gram" | "gram_bf16") at the kept point, factorised and solved in HBM; params: gtol,
+        max_iterations, hessian and the damping constants (NEWTON_DEFAULTS).  -> dict(forces, weights (or None), status
+        (0: max|g| <= gtol, 1: max_iterations, 2: at the minimum to the rounding of f, 3: lambda out of range), fmin, gmax,
+        lam, iterations, evaluations, hessians, factorisations, switched).  The returned point is the context's kept
+        point: forces_gram() right after serves it."""
+        f0, w0 = self._mvec(forces0, "forces0"), self._nvec(w0, "w0")
+        cfg = newton_config(params)
+        out = np.empty(self.m)
+        w = np.empty(self.n) if want_weights else None
+        res = NewtonResult()
+        check(lib().bioen_hip_opt_newton_forces(self._h, ptr(f0), ptr(w0), float(theta), C.byref(cfg), ptr(out),
+                                                ptr(w) if want_weights else None, C.byref(res)))
+        return dict(forces=out, weights=w, status=res.status, fmin=res.fmin, gmax=res.gmax, lam=res.lam,
+                    iterations=res.iterations, evaluations=res.evaluations, hessians=res.hessians,
+                    factorisations=res.factorisations, switched=bool(res.switched))
 
     def forces_colquad(self, P, forces=None, w0=None, theta=None):
         """v[j] = a_j^T P a_j for every structure j, a_j = y_j - ybar the structure's observables (of the affine model if one

@@ -23,6 +23,7 @@
 #include "../../include/bioen_hip_forces_gram.h"
 #include "../../include/bioen_hip_forces_colquad.h"
 #include "../../include/bioen_hip_forces_gram_bf16.h"
+#include "../../include/bioen_hip_forces_newton.h"
 #include "kernels.hpp"
 #include "lbfgs.hpp"
 #include "multimin.hpp"
@@ -1117,6 +1118,7 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
     if (c->fgram_buf) hipFree(c->fgram_buf);
     if (c->fcolquad_buf) hipFree(c->fcolquad_buf);
     if (c->fgram16_buf) hipFree(c->fgram16_buf);
+    if (c->fnewton_buf) hipFree(c->fnewton_buf);
     p2p_release(c);
     comm_release(c);
     resolve_timers(c);
@@ -1267,6 +1269,10 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
     if (c->fgram16_buf) {        // bioen_hip_forces_gram_bf16's sets, their sum, C~ and H~ (api_forces_gram_bf16.inl)
         f |= 128;
         b += c->fgram16_bytes;
+    }
+    if (c->fnewton_buf) {        // the Newton minimizer's L, a caller's matrix and the right-hand sides (api_forces_newton.inl)
+        f |= 256;
+        b += c->fnewton_bytes;
     }
     if (forms) *forms = f;
     if (bytes) *bytes = b;
@@ -2217,3 +2223,4 @@ static void comm_release(bioen_hip_ctx* c) {
 #include "api_forces_gram.inl"
 #include "api_forces_colquad.inl"
 #include "api_forces_gram_bf16.inl"
+#include "api_forces_newton.inl"

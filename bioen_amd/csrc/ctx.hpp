@@ -315,6 +315,14 @@ struct bioen_hip_ctx {
     double* fgram16_buf = nullptr;
     long long fgram16_bytes = 0;
 
+    // the Newton minimizer's factorisation (api_forces_newton.inl): L (mp x mp), then a caller's matrix (m x m), the
+    // right-hand sides (kMaxBatch x mp), the source's diagonal (mp) and the info word -- one buffer of its own, allocated at
+    // the first factorisation, kept until the context is destroyed (bioen_hip_ctx_footprint counts it)
+    double* fnewton_buf = nullptr;
+    long long fnewton_bytes = 0;
+    int fnewton_state = 0;               // 0: no factor yet, 1: L is complete, 2: the last factorisation ended with info != 0
+    int fnewton_info = 0;                // ... that info
+
     // RCCL (lazy, dlopen)
     void* comm = nullptr;
     int comm_rank = 0, comm_nranks = 1;

@@ -204,6 +204,14 @@ void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, 
 void launch_forces_gram_bf16(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
                              const double* qv, const double* ybar, double theta);
 
+// ---- dense FP64 Cholesky factorisation and solves on the device, M <= 1024 (kernels_forces_newton.hip) --------
+constexpr int kFNewtonPanel = 64;           // columns of a panel: a diagonal tile is one wave's, a trailing tile four waves'
+// L (ldl x ldl, ldl >= m) <- chol(lower(src) + lambda I), src m x m with leading dimension lds; dg <- diag(src); *info as
+// LAPACK's dpotrf (0, or index + 1 of the pivot that was not positive: the launches behind it leave at once)
+void launch_fnewton_factor(bioen_hip_ctx* c, const double* src, int lds, double lambda, double* L, int ldl, double* dg, int* info);
+// X [k][ldx] <- (L L^T)^-1 X, k <= kMaxBatch
+void launch_fnewton_solve(bioen_hip_ctx* c, const double* L, int ldl, int k, double* X, int ldx);
+
 // ---- per-structure quadratic forms a_j^T P a_j at a kept forces point (kernels_forces_colquad.hip) -----------
 constexpr int kForcesColquadCols = 32;      // columns of a panel: one block owns them and all M rows
 constexpr int kForcesColquadBlocks = 256;   // blocks of a launch (one per CU); block b runs the panels b, b + 256, ...

@@ -417,6 +417,24 @@ def bioen_opt_lbfgs_forces(forces, w0, yTilde, YTilde, theta, params):
     return res, info.fmin
 
 
+def bioen_opt_newton_forces(forces, w0, yTilde, YTilde, theta, params):
+    """-> (forces_opt[m], fmin): the device-resident Newton minimizer (Context.opt_newton_forces).  Status 0 (max|g| <=
+    gtol) and 2 (at the minimum to the rounding of f) return; 1 (max_iterations) and 3 (the damping left its range) raise
+    RuntimeError with the return code, as the other device minimizers do.  last_opt_info: the result dict."""
+    global last_opt_info
+    ctx, cached = _context_for(yTilde, YTilde)
+    try:
+        res = ctx.opt_newton_forces(forces, w0, theta, params["params"], want_weights=False)
+    finally:
+        _release(ctx, cached)
+    last_opt_info = res
+    if res["status"] not in (0, 2):
+        raise RuntimeError("bioen_opt_newton_forces: return code %d (%s) after %d iterations, max|g| = %.3g"
+                           % (res["status"], {1: "max_iterations reached", 3: "the damping left its range"}.get(
+                               res["status"], "?"), res["iterations"], res["gmax"]))
+    return res["forces"], res["fmin"]
+
+
 # helpers the Python layer uses to keep post-processing on the device ------------------
 def get_weights_logw(g, yTilde, YTilde):
     ctx, cached = _context_for(yTilde, YTilde)

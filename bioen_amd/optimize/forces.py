@@ -372,6 +372,136 @@ def _run_scipy_trust_exact(cfg, f, fprime, hess, x0, args):
     return res.x, res.fun
 
 
+# ------------------------------------------------------------------ the forces method's own Newton minimizer
+# newton:hessian -- where the Newton minimizer's Hessian comes from: "gram" (Context.forces_gram's FP64 pass) or "gram_bf16"
+# (Context.forces_gram_bf16's; the loop goes over to "gram" by itself where the approximate Hessian stops helping)
+_NEWTON_SOURCES = ("gram", "gram_bf16")
+# the damping constants of the loop; the device loop's defaults (bioen_amd._lib.NEWTON_DEFAULTS) are the same
+_NEWTON_CONSTANTS = dict(armijo=1e-4, rho_good=0.75, lambda_factor=4.0, lambda_first=1e-10, lambda_max=1e10,
+                         lambda_zero=1e-12, floor_ulps=8.0)
+NEWTON_STATUS = {0: "max|g| <= gtol", 1: "max_iterations reached", 2: "at the minimum to the rounding of f",
+                 3: "the damping left its range"}
+
+
+def _newton_source(params):
+    """the newton parameter `hessian`, checked: -> "gram" | "gram_bf16" """
+    source = str(params.get("hessian", "gram")).lower()
+    if source not in _NEWTON_SOURCES:
+        raise RuntimeError("newton:hessian=" + source + " not recognized (valid values = 'gram', 'gram_bf16')")
+    return source
+
+
+def _newton_cholesky(H, lam):
+    """(L, info) of H + lam I as the device factorisation reports it: info = 0, or k + 1 where pivot k was <= 0 or not
+    finite (LAPACK dpotrf's convention; only the lower triangle is read)"""
+    import scipy.linalg.lapack as lapack
+    A = np.tril(np.asarray(H, dtype=np.float64))
+    A[np.diag_indices_from(A)] += lam
+    if not np.all(np.isfinite(np.diag(A))):
+        return None, int(np.flatnonzero(~np.isfinite(np.diag(A)))[0]) + 1
+    L, info = lapack.dpotrf(A, lower=1, clean=1)
+    return (L if info == 0 else None), int(info)
+
+
+def newton_bioen_log_posterior_base(forces0, w0, yTilde, YTilde, theta, params, hess=None):
+    """The numpy restatement of Context.opt_newton_forces, the specification of the device loop: regularised
+    Newton on bioen_log_posterior_base with the dense Hessian of `params["hessian"]` ("gram": _hess_gram_base, "gram_bf16":
+    _hess_gram_bf16_base; `hess`, a dict source -> function, replaces them) and a Cholesky factorisation of H + lam I.
+
+      1. max|g| <= gtol -> status 0.           2. H at x from `source`, d = max|diag H|.
+      3. factorise H + lam I; info != 0: lam <- max(4 lam, 1e-10 d), again, no evaluation; lam > 1e10 d -> status 3.
+      4. p = -(L L^T)^-1 g, pred = (-g.p + lam p.p) / 2.        5. f+, g+ at x + p.
+      6. accept if f+ is finite and f+ - f <= -1e-4 pred; at the rounding floor (pred <= 8 eps |f|: f cannot judge the
+         step) if max|g+| < max|g| instead.
+      7. accepted: x <- x + p; (f - f+) / pred > 0.75, or a step at the floor: lam <- lam / 4, 0 below 1e-12 d; to 1.
+      8. rejected at the floor: "gram_bf16" goes over to "gram" (once), H again; "gram" -> status 2: at the minimum to
+         the rounding of f.
+      9. any other rejection: lam <- max(4 lam, 1e-10 d), to 3: no new Hessian.     10. max_iterations accepted steps -> status 1.
+
+    -> dict(forces, status, fmin, gmax, lam, iterations, evaluations, hessians, factorisations, switched)"""
+    import scipy.linalg
+    p_ = dict(_NEWTON_CONSTANTS, **{k: v for k, v in dict(params).items() if k in _NEWTON_CONSTANTS})
+    gtol, maxit = float(params.get("gtol", 1e-6)), int(params.get("max_iterations", 200))
+    source = _newton_source(params)
+    sources = dict({"gram": _hess_gram_base, "gram_bf16": _hess_gram_bf16_base}, **(hess or {}))
+    args = (w0, yTilde, YTilde, theta)
+    eps = np.finfo(np.float64).eps
+
+    def fdf(x):
+        return (float(bioen_log_posterior_base(x, *args)),
+                np.asarray(grad_bioen_log_posterior_base(x, *args), dtype=np.float64).reshape(-1))
+
+    x = np.asarray(forces0, dtype=np.float64).reshape(-1).copy()
+    f, g = fdf(x)
+    lam, d, H, L = 0.0, 1.0, None, None
+    count = dict(iterations=0, evaluations=1, hessians=0, factorisations=0)
+    switched, need_h, status = False, True, None
+
+    def grow(lam):
+        lam = max(p_["lambda_factor"] * lam, p_["lambda_first"] * d)
+        return lam, lam > p_["lambda_max"] * d
+
+    while status is None:
+        gmax = float(np.abs(g).max())
+        if gmax <= gtol:
+            status = 0
+            break
+        if count["iterations"] >= maxit:
+            status = 1
+            break
+        if need_h:
+            H = np.asarray(sources[source](x, *args), dtype=np.float64)
+            count["hessians"] += 1
+            dm = float(np.abs(np.diag(H)).max())
+            d = dm if dm > 0.0 and np.isfinite(dm) else 1.0
+            need_h = False
+        while True:
+            L, info = _newton_cholesky(H, lam)
+            count["factorisations"] += 1
+            if info == 0:
+                break
+            lam, out = grow(lam)
+            if out:
+                status = 3
+                break
+        if status == 3:
+            break
+        p = -scipy.linalg.cho_solve((L, True), g)
+        pred = 0.5 * (-float(g.dot(p))) + 0.5 * lam * float(p.dot(p))
+        ft, gt = fdf(x + p)
+        count["evaluations"] += 1
+        gtmax = float(np.abs(gt).max())
+        floor = pred <= p_["floor_ulps"] * eps * abs(f)
+        accept = bool(np.isfinite(ft)) and (gtmax < gmax if floor else ft - f <= -p_["armijo"] * pred)
+        if accept:
+            if floor or (f - ft) / pred > p_["rho_good"]:
+                lam /= p_["lambda_factor"]
+                if lam < p_["lambda_zero"] * d:
+                    lam = 0.0
+            x, f, g = x + p, ft, gt
+            need_h = True
+            count["iterations"] += 1
+            continue
+        if floor:
+            if source == "gram_bf16":
+                source, switched, need_h = "gram", True, True
+                continue
+            status = 2
+            break
+        lam, out = grow(lam)
+        if out:
+            status = 3
+    return dict(count, forces=x, status=status, fmin=f, gmax=float(np.abs(g).max()), lam=lam, switched=switched)
+
+
+def _newton_finish(who, res):
+    """status 0 and 2 return; 1 and 3 raise as the other device minimizers do"""
+    if res["status"] not in (0, 2):
+        raise RuntimeError("%s: return code %d (%s) after %d iterations, max|g| = %.3g"
+                           % (who, res["status"], NEWTON_STATUS.get(res["status"], "?"), res["iterations"], res["gmax"]))
+    return res["forces"], res["fmin"]
+
+
 # ------------------------------------------------------------------ optimizer
 class _DeviceFdf(object):
     """One fused device evaluation per point for scipy's separate f / f' callbacks."""
@@ -435,15 +565,17 @@ def find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
     duration of the call (ext/c_bioen.py: hold): the initial objective, the optimisation, chi^2 / S and the averages of the
     optimum are served by one device copy -- at most ONE upload per call whatever the size of the matrix."""
     check_params_forces(forcesInit, w0, y, yTilde, YTilde)
-    if str(cfg["minimizer"]).upper() not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY'):      # rejected before anything touches the device
+    if str(cfg["minimizer"]).upper() not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY', 'NEWTON'):      # rejected before anything touches the device
         raise RuntimeError("Library " + cfg["minimizer"] +
-                           " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy' ) ")
+                           " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy', 'newton' ) ")
+    if str(cfg["minimizer"]).upper() == 'NEWTON':
+        _newton_source(cfg["params"])
     if str(cfg["minimizer"]).upper() == 'SCIPY' and cfg["params"].get("on_device"):
         raise RuntimeError("scipy:on_device (scipy's BFGS with the inverse Hessian on the device) serves the "
                            "log-weights method only (optimize.log_weights.find_optimum); the forces method has none")
     if str(cfg["minimizer"]).upper() == 'SCIPY':
         _hessian_source(cfg)
-    if not (str(cfg["minimizer"]).upper() == 'SCIPY' and not bool(cfg["use_c_functions"])):
+    if not (str(cfg["minimizer"]).upper() in ('SCIPY', 'NEWTON') and not bool(cfg["use_c_functions"])):
         with c_bioen.hold(yTilde, YTilde):
             return _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg)
     return _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg)
@@ -461,11 +593,11 @@ def _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
     cfg["cache_ytilde_transposed"] = caching
 
     minimizer = cfg["minimizer"].upper()
-    if minimizer not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY'):
+    if minimizer not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY', 'NEWTON'):
         raise RuntimeError("Library " + cfg["minimizer"] +
-                           " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy' ) ")
+                           " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy', 'newton' ) ")
     use_c = bool(cfg["use_c_functions"])
-    use_device = not (minimizer == 'SCIPY' and not use_c)
+    use_device = not (minimizer in ('SCIPY', 'NEWTON') and not use_c)
 
     if use_device:
         fmin_initial = c_bioen.bioen_log_posterior_forces(forcesInit, w0, yTilde, YTilde, theta)
@@ -485,6 +617,13 @@ def _find_optimum(forcesInit, w0, y, yTilde, YTilde, theta, cfg):
     elif minimizer == 'GSL':
         common.print_highlighted("FORCES -- Library GSL/C", cfg["verbose"])
         res = c_bioen.bioen_opt_bfgs_forces(forces, w0, yTilde, YTilde, theta, cfg)
+    elif minimizer == 'NEWTON' and use_c:
+        common.print_highlighted("FORCES -- Library Newton/HIP", cfg["verbose"])
+        res = c_bioen.bioen_opt_newton_forces(forces, w0, yTilde, YTilde, theta, cfg)
+    elif minimizer == 'NEWTON':
+        common.print_highlighted("FORCES -- Library Newton/PY", cfg["verbose"])
+        res = _newton_finish("newton_bioen_log_posterior_base",
+                             newton_bioen_log_posterior_base(forces, w0, yTilde, YTilde, theta, cfg["params"]))
     elif minimizer == 'SCIPY' and use_c:
         common.print_highlighted("FORCES -- Library scipy/HIP", cfg["verbose"])
         dev = _DeviceFdf(w0, yTilde, YTilde, theta, keep_point=dense, hessian=hessian)
