@@ -851,23 +851,7 @@ class Context(object):
         The first call allocates a device buffer for the partial sums that stays with the context (footprint():
         "forces_gram"): O(sets x m^2) whatever n is -- 117 MB at m = 256, 139 MB at m = 512, 168 MB at m = 1024 -- so with
         many small contexts prefer forces_hessian."""
-        fn = lib().bioen_hip_forces_gram
-        m = self.m
-        C_ = np.empty((m, m)) if cov else None
-        H = np.empty((m, m)) if hess else None
-        pc, ph = (ptr(C_) if cov else None), (ptr(H) if hess else None)
-        if forces is None:
-            if not (cov or hess):
-                raise ValueError("forces_gram without forces needs cov or hess")
-            check(fn(self._h, None, None, 0.0, pc, ph, None, None))
-            return C_, H
-        if w0 is None or theta is None:
-            raise ValueError("forces_gram with forces needs w0 and theta")
-        fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
-        f = C.c_double(0.0)
-        grad = np.empty(m)
-        check(fn(self._h, ptr(fo), ptr(w0), float(theta), pc, ph, C.byref(f), ptr(grad)))
-        return C_, H, f.value, grad
+        return self._forces_gram(lib().bioen_hip_forces_gram, "forces_gram", forces, w0, theta, cov, hess)
 
     def forces_gram_bf16(self, forces=None, w0=None, theta=None, cov=True, hess=True):
         """(C~, H~): forces_gram's C and H with the two M x M x N products formed from split-BF16 operands (every operand
@@ -879,18 +863,21 @@ class Context(object):
         the point is kept; without -> (C~, H~) at the kept point.  Both matrices are bitwise symmetric and the same bits
         call after call.  The first computing call allocates a device buffer of forces_gram's size that stays with the
         context (footprint(): "forces_gram_bf16")."""
-        fn = lib().bioen_hip_forces_gram_bf16
+        return self._forces_gram(lib().bioen_hip_forces_gram_bf16, "forces_gram_bf16", forces, w0, theta, cov, hess)
+
+    def _forces_gram(self, fn, name, forces, w0, theta, cov, hess):
+        """forces_gram and forces_gram_bf16: one call shape, `fn` the entry and `name` the method in the ValueError texts"""
         m = self.m
         C_ = np.empty((m, m)) if cov else None
         H = np.empty((m, m)) if hess else None
         pc, ph = (ptr(C_) if cov else None), (ptr(H) if hess else None)
         if forces is None:
             if not (cov or hess):
-                raise ValueError("forces_gram_bf16 without forces needs cov or hess")
+                raise ValueError("%s without forces needs cov or hess" % name)
             check(fn(self._h, None, None, 0.0, pc, ph, None, None))
             return C_, H
         if w0 is None or theta is None:
-            raise ValueError("forces_gram_bf16 with forces needs w0 and theta")
+            raise ValueError("%s with forces needs w0 and theta" % name)
         fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
         f = C.c_double(0.0)
         grad = np.empty(m)

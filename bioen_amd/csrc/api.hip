@@ -1115,10 +1115,8 @@ int bioen_hip_ctx_destroy(bioen_hip_ctx* c) {
     if (c->stream) hipStreamSynchronize(c->stream);
     bfgs_free(c);
     hessp_free(c);
-    if (c->fgram_buf) hipFree(c->fgram_buf);
-    if (c->fcolquad_buf) hipFree(c->fcolquad_buf);
-    if (c->fgram16_buf) hipFree(c->fgram16_buf);
-    if (c->fnewton_buf) hipFree(c->fnewton_buf);
+    for (const CtxScratchBuf& s : c->scratch)
+        if (s.p) hipFree(s.p);
     p2p_release(c);
     comm_release(c);
     resolve_timers(c);
@@ -1258,22 +1256,11 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
         f |= 16;
         b += c->bfgs_hbytes;
     }
-    if (c->fgram_buf) {          // bioen_hip_forces_gram's sets, their sum, C and H (api_forces_gram.inl)
-        f |= 32;
-        b += c->fgram_bytes;
-    }
-    if (c->fcolquad_buf) {       // bioen_hip_forces_colquad's P and results (api_forces_colquad.inl)
-        f |= 64;
-        b += c->fcolquad_bytes;
-    }
-    if (c->fgram16_buf) {        // bioen_hip_forces_gram_bf16's sets, their sum, C~ and H~ (api_forces_gram_bf16.inl)
-        f |= 128;
-        b += c->fgram16_bytes;
-    }
-    if (c->fnewton_buf) {        // the Newton minimizer's L, a caller's matrix and the right-hand sides (api_forces_newton.inl)
-        f |= 256;
-        b += c->fnewton_bytes;
-    }
+    for (int i = 0; i < SCRATCH_COUNT; ++i)      // the dense forces entries' buffers (ctx.hpp: CtxScratch): 32, 64, 128, 256
+        if (c->scratch[i].p) {
+            f |= 32 << i;
+            b += c->scratch[i].bytes;
+        }
     if (forms) *forms = f;
     if (bytes) *bytes = b;
     return 0;
@@ -2218,9 +2205,9 @@ static void comm_release(bioen_hip_ctx* c) {
 
 #include "api_multimin.inl"
 #include "api_bfgs.inl"
+#include "api_forces_point.inl"
 #include "api_hessp.inl"
 #include "api_forces_hessp.inl"
 #include "api_forces_gram.inl"
 #include "api_forces_colquad.inl"
-#include "api_forces_gram_bf16.inl"
 #include "api_forces_newton.inl"

@@ -1,25 +1,8 @@
 // One quadratic form per structure at a kept forces point (part of api.hip's translation unit: uses its static helpers;
-// kernel: kernels_forces_colquad.hip; the mathematics: DESIGN section 6f).  The point is bioen_hip_forces_hessp's
-// (api_forces_hessp.inl: fhp_set_point), with bioen_hip_forces_gram's semantics.
+// kernel: kernels_forces_colquad.hip; the mathematics: DESIGN section 6f).  The point, the guard and the buffer are
+// api_forces_point.inl's: forces_point_prologue, dense_guard with this entry's reasons, ensure_scratch.
 
 namespace bioen {
-
-// what the entry refuses, each with a message of its own (fgram_guard's set)
-static int fcolquad_guard(const bioen_hip_ctx* c) {
-    if (c->world != 1)
-        return fail(BIOEN_HIP_ESTATE, "bioen_hip_forces_colquad is not served on a structure-sharded context (a rank holds its "
-                                      "own structures' columns only and the entry does not gather the results)");
-    if (c->m > 1024)
-        return fail(BIOEN_HIP_ESTATE, "bioen_hip_forces_colquad serves M <= 1024 only (beyond, the matrix is held as row panels "
-                                      "and a block cannot own all rows of its columns)");
-    if (c->storage)
-        return fail(BIOEN_HIP_ESTATE, "bioen_hip_forces_colquad is not served on the reduced-storage experiment's copies "
-                                      "(bioen_hip_ctx_set_storage(0))");
-    if (forces_fused_blocks(c) <= 0)
-        return fail(BIOEN_HIP_ESTATE, "bioen_hip_forces_colquad needs the strip copies of the matrix: the streaming kernels have "
-                                      "no quadratic form");
-    return 0;
-}
 
 // |P_ij - P_ji| <= 1e-12 max |P| (an inverse formed in floating point is symmetric to rounding, not bit for bit)
 static bool fcolquad_symmetric(const double* P, int m) {
@@ -43,32 +26,15 @@ extern "C" int bioen_hip_forces_colquad(bioen_hip_ctx* c, const double* forces, 
     if (P && !out) return fail(BIOEN_HIP_EINVAL, "P without out");
     if (P && !fcolquad_symmetric(P, c->m)) return fail(BIOEN_HIP_EINVAL, "P is not symmetric");
     int rc;
-    if ((rc = fcolquad_guard(c)) || (rc = forces_guard(c))) return rc;
-    if (forces) {
-        // ... with forces it is an evaluation: bioen_hip_forces_hessp's with k = 0, declared under this entry's name
-        if ((rc = fhp_set_point(c, forces, w0, theta, f, grad, __func__))) return rc;
-    } else {
-        if (!c->point_valid || c->point_kind != 1) {
-            std::string m;
-            if (c->point_valid)
-                m = "the point on this context is a log-weights point (set by bioen_hip_logw_hessp): call bioen_hip_forces_colquad with forces first";
-            else if (c->point_lost)
-                m = std::string("the point of the last call with forces (or g) is gone: dropped by ") + c->point_lost;
-            else
-                m = "no point on this context: call bioen_hip_forces_colquad with forces first";
-            return fail(BIOEN_HIP_ESTATE, m.c_str());
-        }
-        if ((rc = enter(c, FX_DEVICE, __func__))) return rc;
-    }
+    if ((rc = dense_guard(c, __func__, kColquadReasons)) || (rc = forces_guard(c))) return rc;
+    if ((rc = forces_point_prologue(c, forces, w0, theta, f, grad, __func__))) return rc;      // ... with forces it is an evaluation
     if (!P) return 0;
     if (forces_fused_blocks(c) <= 0) return fail(BIOEN_HIP_ESTATE, "the strip passes no longer serve this context");
     if ((rc = ensure_strip_copy(c, 1))) return rc;
     const int m = c->m, mps = (int)round_up((size_t)c->m, 16);      // the strips' rows (M <= 1024: one panel)
     const size_t pcount = (size_t)mps * mps;
-    if (!c->fcolquad_buf) {
-        if ((rc = dalloc_zero(&c->fcolquad_buf, pcount + c->ld, c->stream))) return rc;
-        c->fcolquad_bytes = (long long)((pcount + c->ld) * sizeof(double));
-    }
+    if ((rc = ensure_scratch(c, SCRATCH_COLQUAD, pcount + c->ld))) return rc;
+    double* buf = c->scratch[SCRATCH_COLQUAD].p;
     // P_eff = S P S on the symmetric part of P, padded with zeros to the strip rows: element (i, j) is
     // ((P_ij + P_ji) / 2) (s_i s_j) -- bitwise symmetric, and P_ij itself for an exactly symmetric P and scales of 1
     std::vector<double> sc((size_t)m, 1.0);
@@ -83,11 +49,11 @@ extern "C" int bioen_hip_forces_colquad(bioen_hip_ctx* c, const double* forces, 
             pe[(size_t)i * mps + j] = v;
             pe[(size_t)j * mps + i] = v;
         }
-    BIOEN_HIP_CHECK(hipMemcpyAsync(c->fcolquad_buf, pe.data(), pcount * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    BIOEN_HIP_CHECK(hipMemcpyAsync(buf, pe.data(), pcount * sizeof(double), hipMemcpyHostToDevice, c->stream));
     BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));         // (pe is pageable and leaves scope)
-    launch_forces_colquad(c, c->fcolquad_buf, c->fpoint_ybar, c->fcolquad_buf + pcount);
+    launch_forces_colquad(c, buf, c->fpoint_ybar, buf + pcount);
     if ((rc = check_launch())) return rc;
-    BIOEN_HIP_CHECK(hipMemcpyAsync(out, c->fcolquad_buf + pcount, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BIOEN_HIP_CHECK(hipMemcpyAsync(out, buf + pcount, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
     return 0;
 }

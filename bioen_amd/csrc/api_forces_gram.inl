@@ -1,23 +1,46 @@
 // The dense Hessian and the covariance of the forces objective in one pass (part of api.hip's translation unit: uses its
-// static helpers; kernels: kernels_forces_gram.hip; the mathematics: DESIGN section 6e).  The point is
-// bioen_hip_forces_hessp's (api_forces_hessp.inl: fhp_set_point): a call with forces sets it as that entry does with k = 0.
+// static helpers), from FP64 operands -- bioen_hip_forces_gram; kernels: kernels_forces_gram.hip; DESIGN section 6e -- or
+// from split-BF16 operands on the BF16 matrix cores, for a Newton minimizer -- bioen_hip_forces_gram_bf16; kernel:
+// kernels_forces_gram_bf16.hip; DESIGN section 6g.  Two entries, not two modes of one: each pass has a buffer of its own,
+// so that bioen_hip_forces_gram's results stay bitwise what they are.  Everything else is one function, fgram_entry; the
+// point, the guard and the buffers are api_forces_point.inl's.
 
 namespace bioen {
 
-// what the entry refuses, each with a message of its own
-static int fgram_guard(const bioen_hip_ctx* c) {
-    if (c->world != 1)
-        return fail(BIOEN_HIP_ESTATE, "bioen_hip_forces_gram is not served on a structure-sharded context (the all-gather of "
-                                      "the segments' partial matrices is not built): use bioen_hip_forces_hessp there");
-    if (c->m > 1024)
-        return fail(BIOEN_HIP_ESTATE, "bioen_hip_forces_gram serves M <= 1024 only (beyond, the matrix is held as row panels): "
-                                      "use bioen_hip_forces_hessp there");
-    if (c->storage)
-        return fail(BIOEN_HIP_ESTATE, "bioen_hip_forces_gram is not served on the reduced-storage experiment's copies "
-                                      "(bioen_hip_ctx_set_storage(0))");
-    if (forces_fused_blocks(c) <= 0)
-        return fail(BIOEN_HIP_ESTATE, "bioen_hip_forces_gram needs the strip copies of the matrix: the streaming kernels have no "
-                                      "Gram product");
+// C and H of the kept forces point into the buffer of `source` (0: the FP64 pass, SCRATCH_GRAM; 1: the split-BF16 pass,
+// SCRATCH_GRAM16), not downloaded: *cov, *hess (either may be NULL) <- where they stand on the device.  The Newton
+// entries (api_forces_newton.inl) take their Hessian from here.
+static int fgram_compute(bioen_hip_ctx* c, int source, const double** cov, const double** hess) {
+    int rc;
+    if (forces_fused_blocks(c) <= 0) return fail(BIOEN_HIP_ESTATE, "the strip passes no longer serve this context");
+    if ((rc = ensure_strip_copy(c, 1))) return rc;
+    const ForcesGramPlan p = forces_gram_plan(c);
+    const int which = source ? SCRATCH_GRAM16 : SCRATCH_GRAM;
+    if ((rc = ensure_scratch(c, which, p.doubles))) return rc;
+    double* buf = c->scratch[which].p;
+    const ProblemSlot& s0 = c->slot[0];
+    (source ? launch_forces_gram_bf16 : launch_forces_gram)(c, p, buf, s0.a, s0.scal, c->fpoint_q, c->fpoint_ybar, c->point_theta);
+    if ((rc = check_launch())) return rc;
+    if (cov) *cov = buf + p.cov_at;
+    if (hess) *hess = buf + p.hess_at;
+    return 0;
+}
+
+static int fgram_entry(bioen_hip_ctx* c, int source, const double* forces, const double* w0, double theta, double* cov,
+                       double* hess, double* f, double* grad, const char* who) {
+    if (int rc = enter(c, FX_NONE, who)) return rc;           // a call rejected below leaves the point (and the device) alone
+    if (forces && !w0) return fail(BIOEN_HIP_EINVAL, "forces without w0");
+    if (!forces && !cov && !hess) return fail(BIOEN_HIP_EINVAL, "nothing to do: no forces, no cov and no hess");
+    int rc;
+    if ((rc = dense_guard(c, who, kGramReasons)) || (rc = forces_guard(c))) return rc;
+    if ((rc = forces_point_prologue(c, forces, w0, theta, f, grad, who))) return rc;
+    if (!cov && !hess) return 0;
+    const double *dcov = nullptr, *dhess = nullptr;
+    if ((rc = fgram_compute(c, source, &dcov, &dhess))) return rc;
+    const size_t bytes = (size_t)c->m * c->m * sizeof(double);
+    if (cov) BIOEN_HIP_CHECK(hipMemcpyAsync(cov, dcov, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (hess) BIOEN_HIP_CHECK(hipMemcpyAsync(hess, dhess, bytes, hipMemcpyDeviceToHost, c->stream));
+    BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -25,41 +48,10 @@ static int fgram_guard(const bioen_hip_ctx* c) {
 
 extern "C" int bioen_hip_forces_gram(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* cov,
                                      double* hess, double* f, double* grad) {
-    if (int rc = enter(c, FX_NONE, __func__)) return rc;      // a call rejected below leaves the point (and the device) alone ...
-    if (forces && !w0) return fail(BIOEN_HIP_EINVAL, "forces without w0");
-    if (!forces && !cov && !hess) return fail(BIOEN_HIP_EINVAL, "nothing to do: no forces, no cov and no hess");
-    int rc;
-    if ((rc = fgram_guard(c)) || (rc = forces_guard(c))) return rc;
-    if (forces) {
-        // ... with forces it is an evaluation: bioen_hip_forces_hessp's with k = 0, declared under this entry's name
-        if ((rc = fhp_set_point(c, forces, w0, theta, f, grad, __func__))) return rc;
-    } else {
-        if (!c->point_valid || c->point_kind != 1) {
-            std::string m;
-            if (c->point_valid)
-                m = "the point on this context is a log-weights point (set by bioen_hip_logw_hessp): call bioen_hip_forces_gram with forces first";
-            else if (c->point_lost)
-                m = std::string("the point of the last call with forces (or g) is gone: dropped by ") + c->point_lost;
-            else
-                m = "no point on this context: call bioen_hip_forces_gram with forces first";
-            return fail(BIOEN_HIP_ESTATE, m.c_str());
-        }
-        if ((rc = enter(c, FX_DEVICE, __func__))) return rc;
-    }
-    if (!cov && !hess) return 0;
-    if (forces_fused_blocks(c) <= 0) return fail(BIOEN_HIP_ESTATE, "the strip passes no longer serve this context");
-    if ((rc = ensure_strip_copy(c, 1))) return rc;
-    const ForcesGramPlan p = forces_gram_plan(c);
-    if (!c->fgram_buf) {
-        if ((rc = dalloc_zero(&c->fgram_buf, p.doubles, c->stream))) return rc;
-        c->fgram_bytes = (long long)(p.doubles * sizeof(double));
-    }
-    const ProblemSlot& s0 = c->slot[0];
-    launch_forces_gram(c, p, c->fgram_buf, s0.a, s0.scal, c->fpoint_q, c->fpoint_ybar, c->point_theta);
-    if ((rc = check_launch())) return rc;
-    const size_t bytes = (size_t)c->m * c->m * sizeof(double);
-    if (cov) BIOEN_HIP_CHECK(hipMemcpyAsync(cov, c->fgram_buf + p.cov_at, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (hess) BIOEN_HIP_CHECK(hipMemcpyAsync(hess, c->fgram_buf + p.hess_at, bytes, hipMemcpyDeviceToHost, c->stream));
-    BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return 0;
+    return fgram_entry(c, 0, forces, w0, theta, cov, hess, f, grad, __func__);
+}
+
+extern "C" int bioen_hip_forces_gram_bf16(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* cov,
+                                          double* hess, double* f, double* grad) {
+    return fgram_entry(c, 1, forces, w0, theta, cov, hess, f, grad, __func__);
 }

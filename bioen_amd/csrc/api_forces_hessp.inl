@@ -5,6 +5,8 @@
 // "the point" (ctx.hpp: point_kind 1): slot 0 holds x' and the scalars, c->fixed the prior w0, fpoint_ybar / fpoint_rs the
 // M-vectors ybar' and r o s, fpoint_q the N-vector q - qbar -- ONE column-sum pass more than the evaluation.  A product at
 // the kept point is then two fused matrix passes, what a gradient costs, for up to kMaxBatch directions at once.
+// Whether a call sets the point or serves the kept one, and the refusal without one, is api_forces_point.inl's
+// forces_point_prologue, shared with the dense entries.
 
 namespace bioen {
 
@@ -137,8 +139,9 @@ static int fhp_products(bioen_hip_ctx* c, int k, const double* v, double* hv) {
     return fhp_download(c, k, hv, gm_h);
 }
 
-// Evaluates the point and keeps it on the context, for the entry `who` (this one, bioen_hip_forces_gram): the effects are
-// declared under that name, so the reason recorded for a dropped point names the call the user made.
+// Evaluates the point and keeps it on the context, for the entry `who` (every entry that goes through
+// api_forces_point.inl's forces_point_prologue, and the Newton loop): the effects are declared under that name, so the
+// reason recorded for a dropped point names the call the user made.
 static int fhp_set_point(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* f, double* grad,
                          const char* who) {
     int rc;
@@ -190,21 +193,7 @@ extern "C" int bioen_hip_forces_hessp(bioen_hip_ctx* c, const double* forces, co
     if (!forces && k == 0) return fail(BIOEN_HIP_EINVAL, "nothing to do: no forces and k = 0");
     int rc;
     if ((rc = forces_guard(c)) || (rc = fhp_guard(c))) return rc;
-    if (!forces && (!c->point_valid || c->point_kind != 1)) {
-        std::string m;
-        if (c->point_valid)
-            m = "the point on this context is a log-weights point (set by bioen_hip_logw_hessp): call bioen_hip_forces_hessp with forces first";
-        else if (c->point_lost)
-            m = std::string("the point of the last call with forces (or g) is gone: dropped by ") + c->point_lost;
-        else
-            m = "no point on this context: call bioen_hip_forces_hessp with forces first";
-        return fail(BIOEN_HIP_ESTATE, m.c_str());
-    }
-    if (forces) {                                                    // ... with forces it is an evaluation
-        if ((rc = fhp_set_point(c, forces, w0, theta, f, grad, __func__))) return rc;
-    } else if ((rc = enter(c, FX_DEVICE, __func__))) {
-        return rc;
-    }
+    if ((rc = forces_point_prologue(c, forces, w0, theta, f, grad, __func__))) return rc;      // ... with forces it is an evaluation
     if (k == 0) return 0;
     rc = fhp_products(c, k, v, hv);
     if (rc) point_drop(c, "a product on it that failed");

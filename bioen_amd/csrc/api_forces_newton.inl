@@ -1,27 +1,14 @@
 // The forces method's own Newton minimizer (part of api.hip's translation unit: uses its static helpers; kernels:
-// kernels_forces_newton.hip).  The Hessian stays where bioen_hip_forces_gram / _gram_bf16 leave it, is
-// factorised and solved on the device; the M-vectors stay on the host, as in ForcesBatchEngine; the loop is
-// forces.py's newton_bioen_log_posterior_base, decision for decision.
+// kernels_forces_newton.hip).  The Hessian stays where bioen_hip_forces_gram / _gram_bf16 leave it
+// (api_forces_gram.inl: fgram_compute), is factorised and solved on the device; the M-vectors stay on the host, as in
+// ForcesBatchEngine; the loop is forces.py's newton_bioen_log_posterior_base, decision for decision.  The guard, the
+// refusal without a forces point and the buffer are api_forces_point.inl's, with these entries' wording.
 
 namespace bioen {
 
-// what the entries refuse, each with a message of its own (fgram16_guard's set)
-static int fnewton_guard(const bioen_hip_ctx* c, const char* who) {
-    const std::string w(who);
-    if (c->world != 1)
-        return fail(BIOEN_HIP_ESTATE, (w + " is not served on a structure-sharded context (the Hessian pass is not built "
-                                           "there): use the L-BFGS, or bioen_hip_forces_hessp with a host driver").c_str());
-    if (c->m > 1024)
-        return fail(BIOEN_HIP_ESTATE, (w + " serves M <= 1024 only (beyond, the matrix is held as row panels and there is no "
-                                           "dense Hessian pass): use the L-BFGS there").c_str());
-    if (c->storage)
-        return fail(BIOEN_HIP_ESTATE, (w + " is not served on the reduced-storage experiment's copies "
-                                           "(bioen_hip_ctx_set_storage(0))").c_str());
-    if (forces_fused_blocks(c) <= 0)
-        return fail(BIOEN_HIP_ESTATE, (w + " needs the strip copies of the matrix: the streaming kernels have no Gram "
-                                           "product").c_str());
-    return 0;
-}
+// the refusal without a forces point, as these entries word it (need_point)
+static const PointWords kFNewtonPoint = {"call with forces",
+                                         "set a forces point first (bioen_hip_forces_hessp, bioen_hip_forces_gram with forces)"};
 
 struct FNewtonBuf {
     double *L, *A, *X, *dg;
@@ -33,7 +20,7 @@ static FNewtonBuf fnewton_layout(const bioen_hip_ctx* c) {
     FNewtonBuf b{};
     const size_t mp = (size_t)c->mp, m = (size_t)c->m;
     b.ldl = c->mp;
-    b.L = c->fnewton_buf;
+    b.L = c->scratch[SCRATCH_NEWTON].p;
     b.A = b.L + mp * mp;
     b.X = b.A + m * m;
     b.dg = b.X + (size_t)kMaxBatch * mp;
@@ -42,33 +29,8 @@ static FNewtonBuf fnewton_layout(const bioen_hip_ctx* c) {
 }
 
 static int fnewton_buffers(bioen_hip_ctx* c) {
-    if (c->fnewton_buf) return 0;
     const size_t mp = (size_t)c->mp, m = (size_t)c->m;
-    const size_t doubles = mp * mp + m * m + (size_t)kMaxBatch * mp + mp + 2;
-    if (int rc = dalloc_zero(&c->fnewton_buf, doubles, c->stream)) return rc;
-    c->fnewton_bytes = (long long)(doubles * sizeof(double));
-    return 0;
-}
-
-// H of the kept forces point into its source's buffer (what bioen_hip_forces_gram / _gram_bf16 compute, not downloaded)
-static int fnewton_hessian(bioen_hip_ctx* c, int source, const double** hess) {
-    int rc;
-    if (forces_fused_blocks(c) <= 0) return fail(BIOEN_HIP_ESTATE, "the strip passes no longer serve this context");
-    if ((rc = ensure_strip_copy(c, 1))) return rc;
-    const ForcesGramPlan p = forces_gram_plan(c);
-    double** buf = source ? &c->fgram16_buf : &c->fgram_buf;
-    if (!*buf) {
-        if ((rc = dalloc_zero(buf, p.doubles, c->stream))) return rc;
-        (source ? c->fgram16_bytes : c->fgram_bytes) = (long long)(p.doubles * sizeof(double));
-    }
-    const ProblemSlot& s0 = c->slot[0];
-    if (source)
-        launch_forces_gram_bf16(c, p, *buf, s0.a, s0.scal, c->fpoint_q, c->fpoint_ybar, c->point_theta);
-    else
-        launch_forces_gram(c, p, *buf, s0.a, s0.scal, c->fpoint_q, c->fpoint_ybar, c->point_theta);
-    if ((rc = check_launch())) return rc;
-    *hess = *buf + p.hess_at;
-    return 0;
+    return ensure_scratch(c, SCRATCH_NEWTON, mp * mp + m * m + (size_t)kMaxBatch * mp + mp + 2);
 }
 
 // chol(lower(src) + lambda I) -> the context's L; *info as LAPACK's; dmax (may be NULL): max |diag src|
@@ -109,20 +71,6 @@ static int fnewton_solve(bioen_hip_ctx* c, int k, const double* B, double* X) {
     return 0;
 }
 
-static int fnewton_need_point(const bioen_hip_ctx* c, const char* who) {
-    if (c->point_valid && c->point_kind == 1) return 0;
-    std::string m;
-    if (c->point_valid)
-        m = std::string(who) + ": the point on this context is a log-weights point (set by bioen_hip_logw_hessp): set a forces "
-                               "point first (bioen_hip_forces_hessp, bioen_hip_forces_gram with forces)";
-    else if (c->point_lost)
-        m = std::string(who) + ": the point of the last call with forces is gone: dropped by " + c->point_lost;
-    else
-        m = std::string(who) + ": no point on this context: set a forces point first (bioen_hip_forces_hessp, "
-                               "bioen_hip_forces_gram with forces)";
-    return fail(BIOEN_HIP_ESTATE, m.c_str());
-}
-
 }  // namespace bioen
 
 extern "C" int bioen_hip_forces_newton_factor(bioen_hip_ctx* c, const double* A, int source, double lambda, double* L, int* info) {
@@ -131,15 +79,15 @@ extern "C" int bioen_hip_forces_newton_factor(bioen_hip_ctx* c, const double* A,
     if (!A && source != 0 && source != 1) return fail(BIOEN_HIP_EINVAL, "source must be 0 (gram) or 1 (gram_bf16)");
     if (!(lambda >= 0.0) || !std::isfinite(lambda)) return fail(BIOEN_HIP_EINVAL, "lambda must be finite and >= 0");
     int rc;
-    if ((rc = fnewton_guard(c, __func__)) || (rc = forces_guard(c))) return rc;
-    if (!A && (rc = fnewton_need_point(c, __func__))) return rc;
+    if ((rc = dense_guard(c, __func__, kNewtonReasons)) || (rc = forces_guard(c))) return rc;
+    if (!A && (rc = need_point(c, 1, __func__, &kFNewtonPoint))) return rc;
     if ((rc = enter(c, FX_DEVICE, __func__))) return rc;
     if ((rc = fnewton_buffers(c))) return rc;
     const FNewtonBuf b = fnewton_layout(c);
     const double* src = b.A;
     if (A) {
         if ((rc = h2d_user(c, b.A, A, (size_t)c->m * c->m * sizeof(double)))) return rc;
-    } else if ((rc = fnewton_hessian(c, source, &src))) {
+    } else if ((rc = fgram_compute(c, source, nullptr, &src))) {
         return rc;
     }
     if ((rc = fnewton_factor(c, src, lambda, info, nullptr))) return rc;
@@ -157,13 +105,13 @@ extern "C" int bioen_hip_forces_newton_solve(bioen_hip_ctx* c, int k, const doub
     if (k < 1 || k > kMaxBatch) return fail(BIOEN_HIP_EINVAL, "k must be in [1, 8]");
     if (!B || !X) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     int rc;
-    if ((rc = fnewton_guard(c, __func__))) return rc;
+    if ((rc = dense_guard(c, __func__, kNewtonReasons))) return rc;
     if (c->fnewton_state == 2) {
         const std::string m = "bioen_hip_forces_newton_solve: the last factorisation on this context ended with info = " +
                               std::to_string(c->fnewton_info) + " (no factor)";
         return fail(BIOEN_HIP_ESTATE, m.c_str());
     }
-    if (c->fnewton_state != 1 || !c->fnewton_buf)
+    if (c->fnewton_state != 1 || !c->scratch[SCRATCH_NEWTON].p)
         return fail(BIOEN_HIP_ESTATE, "bioen_hip_forces_newton_solve: no factor on this context: call "
                                       "bioen_hip_forces_newton_factor first");
     if ((rc = enter(c, FX_DEVICE, __func__))) return rc;
@@ -181,7 +129,7 @@ extern "C" int bioen_hip_opt_newton_forces(bioen_hip_ctx* c, const double* force
         return fail(BIOEN_HIP_EINVAL, "bioen_newton_config: gtol >= 0, max_iterations >= 0, lambda_factor > 1, 0 < lambda_first < "
                                       "lambda_max, armijo > 0, floor_ulps >= 0");
     int rc;
-    if ((rc = fnewton_guard(c, __func__)) || (rc = forces_guard(c)) || (rc = fhp_guard(c))) return rc;
+    if ((rc = dense_guard(c, __func__, kNewtonReasons)) || (rc = forces_guard(c)) || (rc = fhp_guard(c))) return rc;
     const int m = c->m;
     const double eps = 2.220446049250313e-16;
     std::vector<double> x(forces0, forces0 + m), g((size_t)m), xt((size_t)m), gt((size_t)m), p((size_t)m);
@@ -200,7 +148,7 @@ extern "C" int bioen_hip_opt_newton_forces(bioen_hip_ctx* c, const double* force
     };
     if ((rc = fhp_set_point(c, x.data(), w0, theta, &f, g.data(), __func__))) return rc;
     res->evaluations = 1;
-    if ((rc = fnewton_guard(c, __func__)) || (rc = fnewton_buffers(c))) return rc;      // (the strip copies exist by now, or never will)
+    if ((rc = dense_guard(c, __func__, kNewtonReasons)) || (rc = fnewton_buffers(c))) return rc;      // (the strip copies exist by now, or never will)
     double gmax = gmax_of(g);
     for (;;) {
         if (gmax <= cfg->gtol) {                             // 1. the gradient test
@@ -217,7 +165,7 @@ extern "C" int bioen_hip_opt_newton_forces(bioen_hip_ctx* c, const double* force
                 ++res->evaluations;
                 at_x = 1;
             }
-            if ((rc = fnewton_hessian(c, source, &hess))) return rc;
+            if ((rc = fgram_compute(c, source, nullptr, &hess))) return rc;
             ++res->hessians;
         }
         int info = 0;                                        // 3. H + lambda I = L L^T
@@ -287,7 +235,7 @@ extern "C" int bioen_hip_opt_newton_forces(bioen_hip_ctx* c, const double* force
     if (weights_out) {
         // an evaluation of f alone hands out the weights (slot 0); the point is set again behind it
         const double theta0 = 0.0;
-        enter(c, FX_EVALUATES, __func__);
+        if ((rc = enter(c, FX_EVALUATES, __func__))) return rc;
         if ((rc = forces_eval(c, 1, x.data(), w0, &theta0, nullptr, nullptr))) return rc;
         if ((rc = download_n(c, weights_out, c->slot[0].w))) return rc;
         BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));

@@ -5,6 +5,7 @@
 // the gradient and the scalars, c->fixed the prior G, point_ybar the raw averages, point_fac every segment's softmax
 // factor.  A product at the kept point is then what a gradient costs: three N-vector sweeps around one forward and one
 // centred adjoint pass -- the context's own pass family, for up to kMaxBatch directions at once.
+// The refusal without a point is api_forces_point.inl's need_point, the forces entries' too.
 
 namespace bioen {
 
@@ -95,17 +96,9 @@ extern "C" int bioen_hip_logw_hessp(bioen_hip_ctx* c, const double* g, const dou
     if (k < 0 || k > kMaxBatch) return fail(BIOEN_HIP_EINVAL, "k must be in [0, 8]");
     if (k > 0 && (!v || !hv)) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (g && !G) return fail(BIOEN_HIP_EINVAL, "g without G");
-    if (!g && c->point_valid && c->point_kind != 0)      // ONE point per context, of either method
-        return fail(BIOEN_HIP_ESTATE, "the point on this context is a forces point (set by bioen_hip_forces_hessp): "
-                                      "call bioen_hip_logw_hessp with g first");
-    if (!g && !c->point_valid) {
-        const std::string m = c->point_lost
-                                  ? std::string("the point of the last bioen_hip_logw_hessp call with g is gone: dropped by ") + c->point_lost
-                                  : std::string("no point on this context: call bioen_hip_logw_hessp with g first");
-        return fail(BIOEN_HIP_ESTATE, m.c_str());
-    }
-    if (int rc = enter(c, g ? FX_EVALUATES : FX_DEVICE, __func__)) return rc;      // ... with g it is an evaluation
     int rc;
+    if (!g && (rc = need_point(c, 0, __func__))) return rc;      // ONE point per context, of either method (api_forces_point.inl)
+    if ((rc = enter(c, g ? FX_EVALUATES : FX_DEVICE, __func__))) return rc;      // ... with g it is an evaluation
     if (g) {
         c->point_lost = "a call that failed to set a new point";
         if ((rc = hessp_buffers(c, 0))) return rc;

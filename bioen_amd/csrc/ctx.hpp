@@ -146,6 +146,23 @@ struct ProblemSlot {
     double* gram = nullptr;   // kGramStride doubles inside ctx->gram
 };
 
+// The device buffers the dense forces entries keep on a context: each allocated at its entry's first computing call
+// (api_forces_point.inl: ensure_scratch), kept until the context is destroyed; bioen_hip_ctx_footprint reports buffer i
+// as form 32 << i with its bytes
+enum CtxScratch : int {
+    SCRATCH_GRAM,        // bioen_hip_forces_gram: the sets' partial Gram matrices, their sum, C and H (kernels.hpp: ForcesGramPlan)
+    SCRATCH_COLQUAD,     // bioen_hip_forces_colquad: P_eff padded to the strip rows, then the n results
+    SCRATCH_GRAM16,      // bioen_hip_forces_gram_bf16: the split-BF16 pass's sets, their sum, C~ and H~ -- beside SCRATCH_GRAM,
+                         // so that the FP64 pass's results stay what they are
+    SCRATCH_NEWTON,      // the Newton minimizer's factorisation (api_forces_newton.inl): L (mp x mp), then a caller's matrix
+                         // (m x m), the right-hand sides (kMaxBatch x mp), the source's diagonal (mp) and the info word
+    SCRATCH_COUNT
+};
+struct CtxScratchBuf {
+    double* p = nullptr;
+    long long bytes = 0;
+};
+
 }  // namespace bioen
 
 struct bioen_hip_ctx {
@@ -299,27 +316,8 @@ struct bioen_hip_ctx {
     double* hp_vec[2 * bioen::kMaxBatch] = {};   // per direction: v | t, then the centred adjoint c, then H v (ld doubles each,
                                                  // allocated at a direction's first use, kept until the context is destroyed)
 
-    // bioen_hip_forces_gram (api_forces_gram.inl): the sets' partial Gram matrices, their sum, C and H on the device;
-    // allocated at the first call, kept until the context is destroyed (bioen_hip_ctx_footprint counts it)
-    double* fgram_buf = nullptr;
-    long long fgram_bytes = 0;
-
-    // bioen_hip_forces_colquad (api_forces_colquad.inl): P_eff padded to the strip rows, then the n results; allocated at
-    // the first call, kept until the context is destroyed (bioen_hip_ctx_footprint counts it)
-    double* fcolquad_buf = nullptr;
-    long long fcolquad_bytes = 0;
-
-    // bioen_hip_forces_gram_bf16 (api_forces_gram_bf16.inl): the split-BF16 pass's sets, their sum, C~ and H~ -- a buffer of
-    // its own beside fgram_buf (the FP64 pass's results stay what they are); allocated at the first computing call, kept
-    // until the context is destroyed (bioen_hip_ctx_footprint counts it)
-    double* fgram16_buf = nullptr;
-    long long fgram16_bytes = 0;
-
-    // the Newton minimizer's factorisation (api_forces_newton.inl): L (mp x mp), then a caller's matrix (m x m), the
-    // right-hand sides (kMaxBatch x mp), the source's diagonal (mp) and the info word -- one buffer of its own, allocated at
-    // the first factorisation, kept until the context is destroyed (bioen_hip_ctx_footprint counts it)
-    double* fnewton_buf = nullptr;
-    long long fnewton_bytes = 0;
+    // the dense forces entries' scratch buffers (bioen::CtxScratch above; api_forces_point.inl: ensure_scratch)
+    bioen::CtxScratchBuf scratch[bioen::SCRATCH_COUNT];
     int fnewton_state = 0;               // 0: no factor yet, 1: L is complete, 2: the last factorisation ended with info != 0
     int fnewton_info = 0;                // ... that info
 

@@ -198,9 +198,12 @@ struct ForcesGramPlan {
 ForcesGramPlan forces_gram_plan(const bioen_hip_ctx* c);
 void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
                         const double* qv, const double* ybar, double theta);
+// what follows the sets, whichever kernel has written them: their sum in its fixed order, the rank corrections, + C C
+// (k_fgram_sum_sets, k_fgram_finish, k_fgram_square, defined in kernels_forces_gram.hip)
+void launch_fgram_tail(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* ybar, double theta);
 
 // the same pass with split-BF16 operands on the BF16 matrix cores (kernels_forces_gram_bf16.hip): the plan, the
-// sets' layout and the finishing kernels are the FP64 pass's, buf is a buffer of its own
+// sets' layout and the tail are the FP64 pass's, buf is a buffer of its own
 void launch_forces_gram_bf16(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
                              const double* qv, const double* ybar, double theta);
 

@@ -267,30 +267,8 @@ ForcesGramPlan forces_gram_plan(const bioen_hip_ctx* c) {
     return p;
 }
 
-// buf: forces_gram_plan's doubles; x, pscal, qv, ybar: the kept point's.  Leaves C at buf + cov_at, H at buf + hess_at.
-void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
-                        const double* qv, const double* ybar, double theta) {
-    FGramArgs q{};
-    q.Ys = c->Ys[0];
-    q.center = c->strip_center;
-    q.mps = panel_mps(c, 0);
-    q.mp = c->mp;
-    q.n = c->n;
-    q.sps = strip_sps(c);
-    q.gs = p.gs;
-    q.ilv = strip_ilv(c);
-    q.nsets = p.nsets;
-    q.nsl = p.nsl;
-    q.ntiles = p.ntiles;
-    q.w0 = c->fixed;
-    q.x = x;
-    q.qv = qv;
-    q.pscal = pscal;
-    q.partial = buf;
-    q.set_stride = p.set_stride;
-    q.rows_at = p.rows_at;
-    const int nblk = 8 * p.ntiles * ((p.nsets + 7) / 8);
-    hipLaunchKernelGGL(k_forces_gram, dim3(nblk), dim3(256), 0, c->stream, q);
+// the sets in buf -> their sum behind them, C at buf + cov_at, H at buf + hess_at (both passes end here)
+void launch_fgram_tail(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* ybar, double theta) {
     double* sum = buf + (size_t)p.nsets * p.set_stride;
     const int sum_blocks = (int)std::min<size_t>((p.set_stride + kBlock - 1) / kBlock, 4096);
     hipLaunchKernelGGL(k_fgram_sum_sets, dim3(sum_blocks), dim3(kBlock), 0, c->stream, buf, p.set_stride, p.set_stride, c->vr,
@@ -299,6 +277,14 @@ void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, 
     hipLaunchKernelGGL(k_fgram_finish, dim3(tb, tb), dim3(256), 0, c->stream, sum, p.rows_at, c->m, theta, ybar, c->row_scale,
                        c->affine, buf + p.cov_at, buf + p.hess_at);
     hipLaunchKernelGGL(k_fgram_square, dim3(tb, tb), dim3(256), 0, c->stream, buf + p.cov_at, c->m, buf + p.hess_at);
+}
+
+// buf: forces_gram_plan's doubles; x, pscal, qv, ybar: the kept point's.  Leaves C at buf + cov_at, H at buf + hess_at.
+void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
+                        const double* qv, const double* ybar, double theta) {
+    hipLaunchKernelGGL(k_forces_gram, dim3(fgram_blocks(p)), dim3(256), 0, c->stream,
+                       fgram_args<FGramArgs>(c, p, buf, x, pscal, qv));
+    launch_fgram_tail(c, p, buf, ybar, theta);
 }
 
 }  // namespace bioen

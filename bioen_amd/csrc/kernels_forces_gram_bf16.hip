@@ -11,8 +11,8 @@
 // and the B operand alike, so the instruction contracts over the strip's 16 columns in a permuted order.  A wave owns a
 // 64 x 64 sub-tile of both matrices (2 x 16 accumulators of 4 floats), a block of four waves a 128 x 128 tile pair I >= J, as
 // in k_forces_gram.  A set's f32 sums leave as doubles on k_forces_gram's layout, so the sets are added IN FP64 in its
-// fixed order by its k_fgram_sum_sets, and k_fgram_finish / k_fgram_square finish them: those three kernels are launched
-// from here as they are.
+// fixed order by its k_fgram_sum_sets, and k_fgram_finish / k_fgram_square finish them: launch_fgram_tail, that file's,
+// launches those three kernels as they are.
 #include "strip.hpp"
 
 namespace bioen {
@@ -20,14 +20,6 @@ namespace bioen {
 typedef float fl4 __attribute__((ext_vector_type(4)));
 typedef short bh4 __attribute__((ext_vector_type(4)));      // four bfloat16: an operand fragment of the 16-deep instruction
 typedef unsigned u2v __attribute__((ext_vector_type(2)));   // the same two registers as they are filled: elements (0, 1) | (2, 3)
-
-// kernels_forces_gram.hip's: the sets' sum and the finishing steps
-__global__ void k_fgram_sum_sets(const double* __restrict__ partial, size_t set_stride, size_t count, int nlocal, int gs,
-                                 double* __restrict__ out);
-__global__ void k_fgram_finish(const double* __restrict__ sum, size_t rows_at, int m, double theta, const double* __restrict__ ybar,
-                               const double* __restrict__ row_scale, bool affine, double* __restrict__ cov,
-                               double* __restrict__ hess);
-__global__ void k_fgram_square(const double* __restrict__ cov, int m, double* __restrict__ hess);
 
 constexpr int kFGram16SubDoubles = 2 * 16 * 4 * 64;     // = kFGramSubDoubles: [matrix 2][h 4][g 4][register 4][lane 64]
 
@@ -212,35 +204,9 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGram16Args q) {
 // buf + cov_at, H~ at buf + hess_at.
 void launch_forces_gram_bf16(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
                              const double* qv, const double* ybar, double theta) {
-    FGram16Args q{};
-    q.Ys = c->Ys[0];
-    q.center = c->strip_center;
-    q.mps = panel_mps(c, 0);
-    q.mp = c->mp;
-    q.n = c->n;
-    q.sps = strip_sps(c);
-    q.gs = p.gs;
-    q.ilv = strip_ilv(c);
-    q.nsets = p.nsets;
-    q.nsl = p.nsl;
-    q.ntiles = p.ntiles;
-    q.w0 = c->fixed;
-    q.x = x;
-    q.qv = qv;
-    q.pscal = pscal;
-    q.partial = buf;
-    q.set_stride = p.set_stride;
-    q.rows_at = p.rows_at;
-    const int nblk = 8 * p.ntiles * ((p.nsets + 7) / 8);
-    hipLaunchKernelGGL(k_forces_gram_bf16, dim3(nblk), dim3(256), 0, c->stream, q);
-    double* sum = buf + (size_t)p.nsets * p.set_stride;
-    const int sum_blocks = (int)std::min<size_t>((p.set_stride + kBlock - 1) / kBlock, 4096);
-    hipLaunchKernelGGL(k_fgram_sum_sets, dim3(sum_blocks), dim3(kBlock), 0, c->stream, buf, p.set_stride, p.set_stride, c->vr,
-                       p.gs, sum);
-    const int tb = (c->m + 15) / 16;
-    hipLaunchKernelGGL(k_fgram_finish, dim3(tb, tb), dim3(256), 0, c->stream, sum, p.rows_at, c->m, theta, ybar, c->row_scale,
-                       c->affine, buf + p.cov_at, buf + p.hess_at);
-    hipLaunchKernelGGL(k_fgram_square, dim3(tb, tb), dim3(256), 0, c->stream, buf + p.cov_at, c->m, buf + p.hess_at);
+    hipLaunchKernelGGL(k_forces_gram_bf16, dim3(fgram_blocks(p)), dim3(256), 0, c->stream,
+                       fgram_args<FGram16Args>(c, p, buf, x, pscal, qv));
+    launch_fgram_tail(c, p, buf, ybar, theta);
 }
 
 }  // namespace bioen

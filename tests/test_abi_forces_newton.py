@@ -1,28 +1,19 @@
-"""The sixth public header, include/bioen_hip_forces_newton.h, held to the rules tests/test_abi_forces_gram_bf16.py holds the
-fifth to: what it declares is exported and bound (in _lib.py's sixth table, and in no other), it is plain C and a C caller
-links against it, its two structs have the layout of the ctypes classes, and every entry has an effect row (DESIGN section
-6c) that is exercised on the GPU."""
+"""The sixth public header, include/bioen_hip_forces_newton.h, held to the rules of tests/abi_header_rules.py: what it
+declares is exported and bound (in _lib.py's sixth table, and in no other), it is plain C and a C caller links against it,
+its two structs have the layout of the ctypes classes, and every entry has an effect row that is
+exercised on the GPU."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
+from abi_header_rules import HeaderRules, bioen_amd, f, v      # noqa: F401 -- bioen_amd is the GPU tests' fixture
 from conftest import ROOT
-from test_entry_effects import ALPHA, BETA, P, Row, estate
+from test_entry_effects import P, Row
 
-HEADER = os.path.join(ROOT, "include", "bioen_hip_forces_newton.h")
 NAMES = ["bioen_hip_forces_newton_factor", "bioen_hip_forces_newton_solve", "bioen_hip_opt_newton_forces"]
-
-
-def _v():
-    return np.random.default_rng(2).standard_normal(P.get().m)
-
-
-def _f():
-    return 1e-3 * np.random.default_rng(3).standard_normal(P.get().m)
 
 
 def _spd():
@@ -33,7 +24,7 @@ def _spd():
 
 def _factor_then_solve(c):
     c.forces_newton_factor(_spd(), want_L=False)
-    c.forces_newton_solve(_v())
+    c.forces_newton_solve(v())
 
 
 # the rows of DESIGN section 6c for this header: the factorisation and the solve keep point and session (with A=None the
@@ -45,24 +36,18 @@ ENTRIES = {
     ],
     "bioen_hip_forces_newton_solve": [Row("keeps", "keeps", _factor_then_solve)],
     "bioen_hip_opt_newton_forces": [
-        Row("sets", "ends", lambda c: c.opt_newton_forces(_f(), P.get().w0, P.get().theta, dict(max_iterations=2))),
+        Row("sets", "ends", lambda c: c.opt_newton_forces(f(), P.get().w0, P.get().theta, dict(max_iterations=2))),
     ],
 }
 
 
-def declared_functions():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(bioen_hip_\w+)\s*\(", src)))
+RULES = HeaderRules("bioen_hip_forces_newton.h", NAMES, "forces_newton", "c_abi_forces_newton_demo", ENTRIES,
+                    points=("keeps", "sets", "needs"))
 
 
 def test_every_declared_symbol_is_exported_bound_and_classified():
     from bioen_amd import _lib
-    names = declared_functions()
-    assert names == NAMES
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    exported = set(line.split()[-1] for line in out.splitlines() if line.strip())
-    assert not [n for n in names if n not in exported]
-    assert sorted(_lib.exported_symbols_forces_newton()) == names         # bound in the sixth table, nothing else there
+    names, exported = RULES.check_declared_exported_bound_and_classified()
     others = (_lib.exported_symbols(), _lib.exported_symbols_forces_hessp(), _lib.exported_symbols_forces_gram(),
               _lib.exported_symbols_forces_colquad(), _lib.exported_symbols_forces_gram_bf16())
     for table in others:                                                  # ... and the other five tables are their headers' alone
@@ -72,13 +57,6 @@ def test_every_declared_symbol_is_exported_bound_and_classified():
     # the other direction: every bioen_hip_* symbol the library exports is declared in one of the six tables
     bound = set(names).union(*others)
     assert not sorted(n for n in exported if n.startswith("bioen_hip_") and n not in bound)
-    L = _lib.lib()
-    for n in names:
-        assert getattr(L, n).argtypes == _lib._SIGNATURES_FORCES_NEWTON[n][1]
-    assert set(ENTRIES) == set(names)                                     # every entry has its effect rows
-    for rows in ENTRIES.values():
-        for row in rows:
-            assert row.how is not None and row.point in ("keeps", "sets", "needs") and row.session in ("ends", "keeps")
 
 
 STRUCT_PROBE = r"""
@@ -120,84 +98,24 @@ def test_struct_layouts_match_the_ctypes_classes(tmp_path):
         _lib.newton_config(dict(hessian="products"))
 
 
-def _build_c_demo(tmp_path):
-    from bioen_amd import _lib
-    exe = str(tmp_path / "c_abi_forces_newton_demo")
-    libdir = os.path.dirname(_lib.LIB_PATH)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "examples", "c_abi_forces_newton_demo.c"), "-L", libdir, "-lbioen_hip",
-                    "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-lm", "-o", exe], check=True)
-    return exe
-
-
 def test_header_is_plain_c_and_a_c_caller_links(tmp_path):
-    exe = _build_c_demo(tmp_path)
-    import bioen_amd
-    if bioen_amd.device_count() == 0:
-        p = subprocess.run([exe], capture_output=True, text=True)
-        assert p.returncode == 77 and "no HIP device" in p.stdout
+    RULES.check_header_is_plain_c_and_a_c_caller_links(tmp_path)
 
 
 @pytest.mark.gpu
 def test_c_caller_runs_the_loop(tmp_path):
-    p = subprocess.run([_build_c_demo(tmp_path)], capture_output=True, text=True, timeout=120)
-    assert p.returncode == 0 and p.stdout.strip().endswith("ok"), (p.stdout, p.stderr)
-
-
-@pytest.fixture(scope="module")
-def bioen_amd():
-    import bioen_amd
-    assert bioen_amd.device_count() >= 1
-    return bioen_amd
-
-
-ROWS = [pytest.param(row, id="%s-%d" % (name[len("bioen_hip_"):], i)) for name in NAMES for i, row in enumerate(ENTRIES[name])]
+    RULES.check_c_caller_runs(tmp_path)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("row", ROWS)
-def test_effect_on_the_point(bioen_amd, row):
-    """`keeps` leaves the products' point alone, `needs` serves the kept forces point and fails without one, `sets` leaves a
-    new forces point"""
-    p = P.get()
-    with bioen_amd.Context(p.yT, p.YT) as ctx:
-        if row.point == "needs":
-            estate(lambda: row.how(ctx), "no point on this context", "bioen_hip_forces_newton_factor")
-        hv, _, _ = ctx.forces_hessp(_v(), forces=_f(), w0=p.w0, theta=p.theta)
-        row.how(ctx)
-        if row.point == "sets":
-            assert not np.array_equal(ctx.forces_hessp(_v()), hv)         # a product at the new point (the optimiser has moved)
-        else:
-            assert np.array_equal(ctx.forces_hessp(_v()), hv)
-        # ... and on a LOG-WEIGHTS point: `sets` replaces it, `needs` is refused and leaves it, `keeps` leaves it
-        hl, _, _ = ctx.logw_hessp(p.v, g=p.x, G=p.G, theta=p.theta)
-        if row.point == "sets":
-            row.how(ctx)
-            estate(lambda: ctx.logw_hessp(p.v), "forces point")
-        else:
-            if row.point == "needs":
-                estate(lambda: row.how(ctx), "log-weights point", "bioen_hip_forces_newton_factor")
-            else:
-                row.how(ctx)
-            assert np.array_equal(ctx.logw_hessp(p.v), hl)
+@pytest.mark.parametrize("row", RULES.rows())
+def test_effect_on_the_point(bioen_amd, row):      # noqa: F811
+    """`keeps` leaves the products' point alone, `needs` serves the kept forces point and fails without one, naming the entry,
+    `sets` leaves a new forces point: the optimiser has moved"""
+    RULES.check_effect_on_the_point(bioen_amd, row, needles=("bioen_hip_forces_newton_factor",), sets_moves=True)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("row", ROWS)
-def test_effect_on_a_session(bioen_amd, row):
-    p = P.get()
-    with bioen_amd.Context(p.yT, p.YT) as ctx:
-        ctx.logw_fdf(p.x, p.G, p.theta)
-        ctx.bfgs_begin(p.x, p.G, p.theta)
-        ctx.bfgs_trial(ALPHA, True)
-        assert "bfgs_hinv" in ctx.footprint()[0]
-        if row.point == "needs":                            # (the session's own calls have dropped every point)
-            estate(lambda: row.how(ctx))
-        else:
-            row.how(ctx)
-        if row.session == "ends":
-            estate(lambda: ctx.bfgs_trial(BETA, False), "ended by another call")
-            assert "bfgs_hinv" not in ctx.footprint()[0]
-        else:
-            f, _ = ctx.bfgs_trial(2 * BETA, False)
-            assert np.isfinite(f)
+@pytest.mark.parametrize("row", RULES.rows())
+def test_effect_on_a_session(bioen_amd, row):      # noqa: F811
+    RULES.check_effect_on_a_session(bioen_amd, row)
