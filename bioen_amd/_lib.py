@@ -191,6 +191,15 @@ _SIGNATURES_FORCES_NEWTON = {
                                               C.POINTER(NewtonResult)]),
 }
 
+# every symbol include/bioen_hip_forces_laplace.h declares (the seventh public header: the Laplace error bars of the forces
+# method without leaving the device; its entries are bioen_laplace_*, the bioen_hip_* names being closed over the six tables
+# above); bound by lib() beside the other six
+ip = C.POINTER(C.c_int)
+_SIGNATURES_FORCES_LAPLACE = {
+    "bioen_laplace_forces_inverse": (C.c_int, [ctx_p, dp, dp, dp, ip]),
+    "bioen_laplace_forces": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp, dp, dp, dp, ip, dp, dp]),
+}
+
 _lib = None
 
 
@@ -218,6 +227,10 @@ def exported_symbols_forces_newton():
     return sorted(_SIGNATURES_FORCES_NEWTON)
 
 
+def exported_symbols_forces_laplace():
+    return sorted(_SIGNATURES_FORCES_LAPLACE)
+
+
 def lib():
     """Load libbioen_hip.so (once).  Raises if it has not been built."""
     global _lib
@@ -229,7 +242,7 @@ def lib():
                 "There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP, _SIGNATURES_FORCES_GRAM, _SIGNATURES_FORCES_COLQUAD,
-                      _SIGNATURES_FORCES_GRAM_BF16, _SIGNATURES_FORCES_NEWTON):
+                      _SIGNATURES_FORCES_GRAM_BF16, _SIGNATURES_FORCES_NEWTON, _SIGNATURES_FORCES_LAPLACE):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)          # AttributeError here = header/library mismatch
                 fn.restype = res
@@ -524,12 +537,12 @@ class Context(object):
         """(forms, bytes) of the resident copies of the matrix: forms is a set out of {"rowmajor", "strips", "strips_colsum"};
         plus "bfgs_hinv" and its N x N bytes while a BFGS session (bfgs_logw) is live, and "forces_gram", the device buffer
         of forces_gram, "forces_colquad", the one of forces_colquad, "forces_gram_bf16", the one of forces_gram_bf16, and
-        "forces_newton", the factor L and the work buffers of forces_newton_factor / opt_newton_forces, each from its first
-        call on"""
+        "forces_newton", the factor L and the work buffers of forces_newton_factor / opt_newton_forces, and "forces_laplace",
+        the inverse factor and the covariances of forces_inverse / forces_laplace, each from its first call on"""
         f, b = C.c_int(0), C.c_longlong(0)
         check(lib().bioen_hip_ctx_footprint(self._h, C.byref(f), C.byref(b)))
         names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced", 16: "bfgs_hinv", 32: "forces_gram",
-                 64: "forces_colquad", 128: "forces_gram_bf16", 256: "forces_newton"}
+                 64: "forces_colquad", 128: "forces_gram_bf16", 256: "forces_newton", 512: "forces_laplace"}
         return {names[k] for k in names if f.value & k}, b.value
 
     def layout(self):
@@ -934,6 +947,60 @@ class Context(object):
         return dict(forces=out, weights=w, status=res.status, fmin=res.fmin, gmax=res.gmax, lam=res.lam,
                     iterations=res.iterations, evaluations=res.evaluations, hessians=res.hessians,
                     factorisations=res.factorisations, switched=bool(res.switched))
+
+    def forces_inverse(self, A=None):
+        """(Ainv or None, logdet, info): the inverse of a symmetric positive definite (m, m) matrix A (only its lower triangle
+        is read) from its FP64 Cholesky factor, on the device (M <= 1024): Ainv = W^T W with W = L^-1, bitwise
+        symmetric, and logdet = 2 sum ln L_ii.  A=None: the Hessian (forces_gram's) of the kept forces point; the inverse
+        then stays on the device and None is returned for it.  info is LAPACK dpotrf's: 0, or k + 1 where pivot k was <= 0
+        or not finite -- an ordinary result: (None, nan, info).  The factor becomes the context's: forces_newton_solve
+        afterwards solves with it.  The same bits in give the same bits out.  Keeps point and session; the first call
+        allocates a device buffer of 4 padded m^2 doubles that stays with the context (footprint(): "forces_laplace")."""
+        m = self.m
+        pa, Ainv = None, None
+        if A is not None:
+            A = as_f64(A)
+            if A.shape != (m, m):
+                raise ValueError("A must have shape (%d, %d)" % (m, m))
+            pa = ptr(A)
+            Ainv = np.empty((m, m))
+        logdet, info = C.c_double(float("nan")), C.c_int(0)
+        check(lib().bioen_laplace_forces_inverse(self._h, pa, ptr(Ainv) if Ainv is not None else None, C.byref(logdet),
+                                                 C.byref(info)))
+        return (Ainv if info.value == 0 else None), logdet.value, info.value
+
+    def forces_laplace(self, forces=None, w0=None, theta=None, matrices=True):
+        """The Laplace error bars at a forces point, formed on the device (M <= 1024): H from forces_gram's pass,
+        factorised and inverted in HBM, the inverse handed to forces_colquad's pass where it stands.  With `forces` (and w0,
+        theta) the point is evaluated first, as by forces_fdf, and kept; without, the kept forces point is served
+        (BioenHipError as forces_hessp raises it).  -> dict: info (LAPACK dpotrf's; != 0: every array below is None and
+        logdet_H, min_pivot are nan), std_forces (m,), std_averages (m,), var_logw (n,), logdet_H, min_pivot = min L_ii^2,
+        cov_forces and cov_averages ((m, m), bitwise symmetric; None with matrices=False, when nothing of size m^2 comes
+        down), and with forces f and grad.  The first call allocates a device buffer that stays with the context
+        (footprint(): "forces_laplace")."""
+        m = self.m
+        sf, sa, vl = np.empty(m), np.empty(m), np.empty(self.n)
+        cf = np.empty((m, m)) if matrices else None
+        ca = np.empty((m, m)) if matrices else None
+        logdet, pivot, info = C.c_double(float("nan")), C.c_double(float("nan")), C.c_int(0)
+        out = [ptr(sf), ptr(sa), ptr(vl), ptr(cf) if matrices else None, ptr(ca) if matrices else None, C.byref(logdet),
+               C.byref(pivot), C.byref(info)]
+        res = {}
+        if forces is None:
+            check(lib().bioen_laplace_forces(self._h, None, None, 0.0, *(out + [None, None])))
+        else:
+            if w0 is None or theta is None:
+                raise ValueError("forces_laplace with forces needs w0 and theta")
+            fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
+            f = C.c_double(0.0)
+            grad = np.empty(m)
+            check(lib().bioen_laplace_forces(self._h, ptr(fo), ptr(w0), float(theta), *(out + [C.byref(f), ptr(grad)])))
+            res.update(f=f.value, grad=grad)
+        ok = info.value == 0
+        res.update(info=info.value, logdet_H=logdet.value, min_pivot=pivot.value,
+                   std_forces=sf if ok else None, std_averages=sa if ok else None, var_logw=vl if ok else None,
+                   cov_forces=cf if ok else None, cov_averages=ca if ok else None)
+        return res
 
     def forces_colquad(self, P, forces=None, w0=None, theta=None):
         """v[j] = a_j^T P a_j for every structure j, a_j = y_j - ybar the structure's observables (of the affine model if one

@@ -24,6 +24,7 @@
 #include "../../include/bioen_hip_forces_colquad.h"
 #include "../../include/bioen_hip_forces_gram_bf16.h"
 #include "../../include/bioen_hip_forces_newton.h"
+#include "../../include/bioen_hip_forces_laplace.h"
 #include "kernels.hpp"
 #include "lbfgs.hpp"
 #include "multimin.hpp"
@@ -54,6 +55,7 @@ static void hessp_free(bioen_hip_ctx* c);     // the buffers of the Hessian-vect
 
 // The point a Hessian-vector product refers to (api_hessp.inl) is gone; `by`: an entry's name, or what failed
 static void point_drop(bioen_hip_ctx* c, const char* by) {
+    c->fgram_fresh = 0;
     if (c->point_valid) {
         c->point_valid = 0;
         c->point_lost = by;
@@ -1256,7 +1258,7 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
         f |= 16;
         b += c->bfgs_hbytes;
     }
-    for (int i = 0; i < SCRATCH_COUNT; ++i)      // the dense forces entries' buffers (ctx.hpp: CtxScratch): 32, 64, 128, 256
+    for (int i = 0; i < SCRATCH_COUNT; ++i)      // the dense forces entries' buffers (ctx.hpp: CtxScratch): 32, 64, 128, 256, 512
         if (c->scratch[i].p) {
             f |= 32 << i;
             b += c->scratch[i].bytes;
@@ -2211,3 +2213,4 @@ static void comm_release(bioen_hip_ctx* c) {
 #include "api_forces_gram.inl"
 #include "api_forces_colquad.inl"
 #include "api_forces_newton.inl"
+#include "api_forces_laplace.inl"

@@ -12,6 +12,7 @@ namespace bioen {
 // entries (api_forces_newton.inl) take their Hessian from here.
 static int fgram_compute(bioen_hip_ctx* c, int source, const double** cov, const double** hess) {
     int rc;
+    if (!source) c->fgram_fresh = 0;
     if (forces_fused_blocks(c) <= 0) return fail(BIOEN_HIP_ESTATE, "the strip passes no longer serve this context");
     if ((rc = ensure_strip_copy(c, 1))) return rc;
     const ForcesGramPlan p = forces_gram_plan(c);
@@ -21,6 +22,7 @@ static int fgram_compute(bioen_hip_ctx* c, int source, const double** cov, const
     const ProblemSlot& s0 = c->slot[0];
     (source ? launch_forces_gram_bf16 : launch_forces_gram)(c, p, buf, s0.a, s0.scal, c->fpoint_q, c->fpoint_ybar, c->point_theta);
     if ((rc = check_launch())) return rc;
+    if (!source) c->fgram_fresh = 1;                          // (bioen_laplace_forces at the same kept point takes them as they stand)
     if (cov) *cov = buf + p.cov_at;
     if (hess) *hess = buf + p.hess_at;
     return 0;

@@ -156,6 +156,8 @@ enum CtxScratch : int {
                          // so that the FP64 pass's results stay what they are
     SCRATCH_NEWTON,      // the Newton minimizer's factorisation (api_forces_newton.inl): L (mp x mp), then a caller's matrix
                          // (m x m), the right-hand sides (kMaxBatch x mp), the source's diagonal (mp) and the info word
+    SCRATCH_LAPLACE,     // the Laplace error bars (api_forces_laplace.inl): W = L^-1, H^-1, B = W C and C H^-1 C (mp x mp each), then
+                         // diag L, diag H^-1 and diag C H^-1 C (mp each)
     SCRATCH_COUNT
 };
 struct CtxScratchBuf {
@@ -318,6 +320,7 @@ struct bioen_hip_ctx {
 
     // the dense forces entries' scratch buffers (bioen::CtxScratch above; api_forces_point.inl: ensure_scratch)
     bioen::CtxScratchBuf scratch[bioen::SCRATCH_COUNT];
+    int fgram_fresh = 0;                 // 1: SCRATCH_GRAM holds C and H of the kept forces point (fgram_compute, source 0); goes with the point
     int fnewton_state = 0;               // 0: no factor yet, 1: L is complete, 2: the last factorisation ended with info != 0
     int fnewton_info = 0;                // ... that info
 

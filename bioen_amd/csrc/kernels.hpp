@@ -215,6 +215,16 @@ void launch_fnewton_factor(bioen_hip_ctx* c, const double* src, int lds, double 
 // X [k][ldx] <- (L L^T)^-1 X, k <= kMaxBatch
 void launch_fnewton_solve(bioen_hip_ctx* c, const double* L, int ldl, int k, double* X, int ldx);
 
+// ---- from the resident factor to the Laplace error bars, M <= 1024 (kernels_forces_laplace.hip) ---------------
+// W (ldw x ldw) <- L^-1, Hi (m x m, dense, bitwise symmetric) <- W^T W, ldiag <- diag L
+void launch_flaplace_inverse(bioen_hip_ctx* c, const double* L, int ldl, double* W, int ldw, double* Hi, double* ldiag);
+// B (ldb x ldb) <- W Cm, Ca (m x m, dense, bitwise symmetric) <- B^T B; Cm: m x m, dense, symmetric
+void launch_flaplace_averages(bioen_hip_ctx* c, const double* W, int ldw, const double* Cm, double* B, int ldb, double* Ca);
+// P (mps x mps: k_forces_colquad's P_eff) <- Hi_ij (scale_i scale_j) (scale == NULL: Hi_ij), zero beyond m; dg <- diag Hi,
+// dg + ldg <- diag Ca (Ca may be NULL)
+void launch_flaplace_to_colquad(bioen_hip_ctx* c, const double* Hi, const double* Ca, const double* scale, double* P, int mps, double* dg,
+                                int ldg);
+
 // ---- per-structure quadratic forms a_j^T P a_j at a kept forces point (kernels_forces_colquad.hip) -----------
 constexpr int kForcesColquadCols = 32;      // columns of a panel: one block owns them and all M rows
 constexpr int kForcesColquadBlocks = 256;   // blocks of a launch (one per CU); block b runs the panels b, b + 256, ...

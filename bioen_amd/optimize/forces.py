@@ -294,7 +294,7 @@ def _laplace_inverse(H, theta):
     return 0.5 * (Hi + Hi.T)
 
 
-def laplace_error_bars(forces, w0, y, yTilde, YTilde, theta, use_c=True, caching=False):
+def laplace_error_bars(forces, w0, y, yTilde, YTilde, theta, use_c=True, caching=False, on_device=False, matrices=True):
     """Laplace error bars at an optimum `forces` of the forces objective, the negative log-posterior L = theta KL + chi^2 / 2:
     the forces are Gaussian around it with covariance inv(H), and d ybar / d forces = C, d ln w_j / d forces = a_j.  -> dict:
 
@@ -304,9 +304,20 @@ def laplace_error_bars(forces, w0, y, yTilde, YTilde, theta, use_c=True, caching
       var_logw (n,): a_j^T inv(H) a_j,  std_w = w sqrt(var_logw)
 
     use_c: C and H from Context.forces_gram and var_logw from Context.forces_colquad at one kept point of a resident
-    context (M <= 1024); else the numpy restatements.  ValueError if H is not positive definite.  `y` unused."""
+    context (M <= 1024); else the numpy restatements.  ValueError if H is not positive definite.  `y` unused.
+
+    on_device=True: the dict gains logdet_H = ln det H.  With use_c it comes from one Context.forces_laplace
+    call, plus the weights (and with matrices the forces_gram call that sets the point and hands out C and H): H is factorised and inverted where forces_gram leaves it, and the inverse
+    is handed to forces_colquad's pass on the device; with matrices=False the four (m, m) arrays C, H, cov_forces and
+    cov_averages are None and nothing of size m^2 is downloaded.  Without use_c it is the numpy path, with logdet_H = 2 sum
+    ln diag(cholesky(H)): the restatement the device is checked against.  H is judged as _laplace_inverse judges it: on
+    info != 0 or min L_ii^2 <= 1e-13 max|H| the Hessian is downloaded and _laplace_inverse raises its ValueError.
+    (matrices=False knows max|H| only from below -- the larger of max_i 1 / var_forces_i and det(H)^(1/m), both <= max_i
+    H_ii --, so a pivot within a few digits of the threshold may pass there.)"""
     f = np.asarray(forces, dtype=np.float64).reshape(-1)
     w0v = np.asarray(w0, dtype=np.float64).reshape(-1)
+    if on_device:
+        return _laplace_error_bars_on_device(f, w0v, yTilde, YTilde, theta, use_c, matrices)
     if use_c:
         ctx, cached = c_bioen._context_for(yTilde, YTilde)
         try:
@@ -328,6 +339,49 @@ def laplace_error_bars(forces, w0, y, yTilde, YTilde, theta, use_c=True, caching
             "cov_forces": Hi, "std_forces": np.sqrt(np.diag(Hi)),
             "cov_averages": cov_av, "std_averages": np.sqrt(np.maximum(np.diag(cov_av), 0.0)),
             "var_logw": var_logw, "std_w": w * np.sqrt(var_logw)}
+
+
+def _laplace_error_bars_on_device(f, w0v, yTilde, YTilde, theta, use_c, matrices):
+    """laplace_error_bars(on_device=True): see there"""
+    if not use_c:
+        C, H = hessian_gram_bioen_log_posterior_base(f, w0v, yTilde, YTilde, theta)
+        Hi = _laplace_inverse(H, theta)
+        logdet = 2.0 * float(np.log(np.diag(np.linalg.cholesky(H))).sum())
+        var_logw = np.maximum(colquad_bioen_log_posterior_base(f, Hi, w0v, yTilde, YTilde, theta), 0.0)
+        w = get_weights_from_forces(w0v, np.asarray(yTilde, dtype=np.float64), f)[:, 0]
+        cov_av = C.dot(Hi).dot(C)
+        cov_av = 0.5 * (cov_av + cov_av.T)
+        out = {"w": w, "C": C, "H": H,
+               "cov_forces": Hi, "std_forces": np.sqrt(np.diag(Hi)),
+               "cov_averages": cov_av, "std_averages": np.sqrt(np.maximum(np.diag(cov_av), 0.0)),
+               "var_logw": var_logw, "std_w": w * np.sqrt(var_logw), "logdet_H": logdet}
+        if not matrices:
+            out.update(C=None, H=None, cov_forces=None, cov_averages=None)
+        return out
+    ctx, cached = c_bioen._context_for(yTilde, YTilde)
+    try:
+        C = H = None
+        if matrices:
+            C, H, _, _ = ctx.forces_gram(forces=f, w0=w0v, theta=theta)
+            r = ctx.forces_laplace()                 # at the kept point: the pass's C and H serve where they stand
+            scale = float(np.abs(H).max())
+        else:
+            r = ctx.forces_laplace(forces=f, w0=w0v, theta=theta, matrices=False)
+            if r["info"] == 0:
+                scale = max(float((1.0 / r["std_forces"] ** 2).max()), float(np.exp(r["logdet_H"] / f.size)))
+        if r["info"] != 0 or not r["min_pivot"] > 1e-13 * scale:
+            _laplace_inverse(H if H is not None else ctx.forces_gram(cov=False)[1], theta)      # raises: indefinite or singular, in its words
+            if r["info"] != 0:
+                raise ValueError("laplace_error_bars: the Hessian is singular (the device factorisation ended at pivot %d)"
+                                 % r["info"])
+        w = np.asarray(ctx.forces_weights(f, w0v), dtype=np.float64).reshape(-1)      # (an evaluation: the point goes)
+    finally:
+        c_bioen._release(ctx, cached)
+    var_logw = np.maximum(r["var_logw"], 0.0)
+    return {"w": w, "C": C, "H": H,
+            "cov_forces": r["cov_forces"], "std_forces": r["std_forces"],
+            "cov_averages": r["cov_averages"], "std_averages": r["std_averages"],
+            "var_logw": var_logw, "std_w": w * np.sqrt(var_logw), "logdet_H": r["logdet_H"]}
 
 
 # The driver that fits M unknowns with a dense Hessian.  (trust-krylov is not offered: scipy 1.15.3's failed to converge

@@ -3,7 +3,10 @@
 deviations of the forces and of the refined averages, and the five structures whose refined weights are least certain
 (needs the built library and a GPU; there is no CPU path).
 
-    make -C bioen_amd/csrc && python examples/forces_error_bars.py [N] [M] [theta]
+    make -C bioen_amd/csrc && python examples/forces_error_bars.py [--on-device] [N] [M] [theta]
+
+--on-device: the Hessian is factorised and inverted in device memory and handed to the quadratic-form pass there
+(laplace_error_bars(on_device=True, matrices=False)): only the M + N numbers of the error bars and ln det H come down.
 """
 import os
 import sys
@@ -13,9 +16,11 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bioen_amd import optimize                     # noqa: E402  (drop-in for `from bioen import optimize`)
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
-M = int(sys.argv[2]) if len(sys.argv) > 2 else 64
-theta = float(sys.argv[3]) if len(sys.argv) > 3 else 10.0
+on_device = "--on-device" in sys.argv[1:]
+argv = [a for a in sys.argv[1:] if a != "--on-device"]
+N = int(argv[0]) if len(argv) > 0 else 20000
+M = int(argv[1]) if len(argv) > 1 else 64
+theta = float(argv[2]) if len(argv) > 2 else 10.0
 
 # synthetic ensemble after bioen/optimize/forces.py:19-68
 rng = np.random.default_rng(12345)
@@ -33,7 +38,11 @@ wopt, yopt, fopt, f0, fmin, chi2, S = optimize.forces.find_optimum(np.zeros((M, 
 print("theta %g: L %.6f -> %.6f, chi2/2 = %.4f, S = %.4f" % (theta, f0, fmin, chi2, S))
 
 # 2. error bars at the optimum: C and H from forces_gram, Var(ln w_j) = a_j^T inv(H) a_j from forces_colquad, one kept point
-eb = optimize.forces.laplace_error_bars(fopt, w0, y, yTilde, YTilde, theta)
+if on_device:
+    eb = optimize.forces.laplace_error_bars(fopt, w0, y, yTilde, YTilde, theta, on_device=True, matrices=False)
+    print("on the device: ln det H = %.6f" % eb["logdet_H"])
+else:
+    eb = optimize.forces.laplace_error_bars(fopt, w0, y, yTilde, YTilde, theta)
 print("forces:   largest |f| = %.4g, standard deviations %.3g ... %.3g" % (np.abs(fopt).max(), eb["std_forces"].min(),
                                                                           eb["std_forces"].max()))
 print("averages: standard deviations of ybar (units of yTilde) %.3g ... %.3g" % (eb["std_averages"].min(),
