@@ -12,6 +12,7 @@ namespace bioen {
 
 
 typedef double d2 __attribute__((ext_vector_type(2)));
+typedef double d4 __attribute__((ext_vector_type(4)));      // an accumulator of v_mfma_f64_16x16x4_f64
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
@@ -23,6 +24,20 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;   // every lane holds the sum
+}
+
+// the sum over the wave's four quarters (lanes l, l ^ 16, l ^ 32, l ^ 48), in every lane: what the four k-lanes of a matrix
+// instruction's row hold between them
+__device__ __forceinline__ double quad_sum(double t) {
+    t += __shfl_xor(t, 16, 64);
+    t += __shfl_xor(t, 32, 64);
+    return t;
+}
+
+// tile b of a lower triangle numbered row by row -> (ti, tj), tj <= ti: b = ti (ti + 1) / 2 + tj
+__device__ __forceinline__ void tile_pair(int b, int& ti, int& tj) {
+    ti = 0, tj = b;
+    while (tj > ti) tj -= ++ti;
 }
 
 __device__ __forceinline__ double wave_max(double v) {

@@ -187,7 +187,8 @@ void launch_forces_hp_tangent(bioen_hip_ctx* c, const struct ForcesRound& fr);  
 void launch_forces_hp_product(bioen_hip_ctx* c, const struct ForcesRound& fr);         // [matrix pass 2]
 void launch_forces_colsum(bioen_hip_ctx* c, const double* u_c, double* out);           // out = Y'^T u on the forces passes' copy
 
-// ---- dense Hessian and covariance of the forces objective in one pass (kernels_forces_gram.hip) -----------
+// ---- dense Hessian and covariance of the forces objective in one pass (kernels_forces_gram.hip; what its
+// kernel shares with the BF16 pass's: fgram.hpp) ---------------------------------------------------------------------------
 struct ForcesGramPlan {
     int nsl, ntiles, nsub;          // 64-row slices, 128-row tile pairs I >= J, 64 x 64 sub-tiles of the lower triangle
     int gs, nsets;                  // groups per canonical segment; sets of this context (local segments x gs)

@@ -21,8 +21,6 @@
 
 namespace bioen {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-
 constexpr int kCqStrips = kForcesColquadCols / kStripCols;      // strips of a panel
 constexpr int kCqPitch = 40;                                    // doubles per row of the LDS image (32 + 8: the four row quads of an operand fetch start 16 banks apart)
 constexpr int kCqChunks = kCqStrips * (kWaveRows / 8) / 4;      // chunks of a slice per wave: 4
@@ -165,9 +163,7 @@ __global__ __launch_bounds__(256, 1) void k_forces_colquad(ColquadArgs q) {
 
 #pragma unroll
         for (int jb = 0; jb < kCqStrips; ++jb) {
-            double t = sum[jb];
-            t += __shfl_xor(t, 16, 64);
-            t += __shfl_xor(t, 32, 64);
+            const double t = quad_sum(sum[jb]);
             if (lq == 0) red[wave][kStripCols * jb + lr] = t;
         }
         __syncthreads();

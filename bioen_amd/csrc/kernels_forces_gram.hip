@@ -16,32 +16,11 @@
 // (set, sub-tile) has exactly one writer; k_fgram_sum_sets adds the sets in the fixed order
 //   sum over segments (in index order) of [ the segment's groups added in turn ]
 // -- no floating-point atomics, and the shape of the sum is a function of (segcols, M) alone.
-#include "strip.hpp"
+// The arguments, a wave's decode, its centres, the matrix fetch and the row sums' way out are fgram.hpp's: the BF16 pass
+// (kernels_forces_gram_bf16.hip) runs the same ones.
+#include "fgram.hpp"
 
 namespace bioen {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-constexpr int kFGramSubDoubles = 2 * 16 * 4 * 64;      // a sub-tile of both matrices: [matrix 2][h 4][g 4][register 4][lane 64]
-
-struct FGramArgs {
-    const double* Ys;       // row-sum order strip copy
-    const double* center;   // mp values
-    int mps, mp, n;
-    int sps, gs, ilv;       // strips per segment, groups per segment, interleave of the copy
-    int nsets;              // local segments x gs
-    int nsl, ntiles;        // 64-row slices; 128-row tile pairs I >= J
-    const double* w0;       // the point: prior, x', q - qbar, scalar slot (S_LOGS)
-    const double* x;
-    const double* qv;
-    const double* pscal;
-    double* partial;        // [set][sub-tile (si, sj <= si)][kFGramSubDoubles] | [set][row]: row sums of Y' u2
-    size_t set_stride;      // doubles per set
-    size_t rows_at;         // where a set's row sums begin
-};
-
-// index of sub-tile (si, sj), sj <= si, among the lower triangle's
-__host__ __device__ inline int fgram_sub(int si, int sj) { return si * (si + 1) / 2 + sj; }
 
 struct FGramRegs {
     d2 a[kWaveRows / 8];
@@ -49,43 +28,19 @@ struct FGramRegs {
     double w0[4], x[4], qv[4];       // the strip's columns 4 qq + (lane >> 4), qq = 0 .. 3
 };
 
-// Blocks b and b + 8 share an XCD and its L2: the tiles of one set are numbered so that they land on one XCD, next to each
-// other in dispatch order -- they read the same strips.
 __global__ __launch_bounds__(256, 1) void k_forces_gram(FGramArgs q) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lq = lane >> 4, lr = lane & 15;
-    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int set = (k / q.ntiles) * 8 + xcd;
-    if (set >= q.nsets) return;
-    int ti = 0, tj = k % q.ntiles;
-    while (tj > ti) tj -= ++ti;                     // tile pair (ti, tj), tj <= ti
-    const int si = 2 * ti + (wave >> 1), sj = 2 * tj + (wave & 1);
-    if (si >= q.nsl || sj > si) return;             // (no barrier in this kernel: a wave may leave)
-    const int v = set / q.gs, g = set - v * q.gs;
-    const int tg = (q.sps - g + q.gs - 1) / q.gs;   // strips of the set (g < gs <= sps: at least one)
-    const int ra = si * kWaveRows, rb = sj * kWaveRows;
-    int offa[kWaveRows / 8], offb[kWaveRows / 8];
-    strip_chunk_offsets(q.mps, ra, offa);
-    strip_chunk_offsets(q.mps, rb, offb);
-    const size_t wa = (size_t)ra * kStripCols + (size_t)lane * 2, wb = (size_t)rb * kStripCols + (size_t)lane * 2;
+    FGramWave w;
+    if (!fgram_decode(q, lane, wave, w)) return;
     const double logs = q.pscal[S_LOGS];
-
     double ca[4], cb[4];                            // the centres of the lane's rows
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        const int rowa = ra + 16 * h + lr, rowb = rb + 16 * h + lr;
-        ca[h] = rowa < q.mp ? q.center[rowa] : 0.0;
-        cb[h] = rowb < q.mp ? q.center[rowb] : 0.0;
-    }
+    fgram_centres(q, w, lr, ca, cb);
 
     auto fetch = [&](int i, FGramRegs& r) {
-        const int s = v * q.sps + g + q.gs * i;
-        const double* src = q.Ys + (size_t)strip_phys(s, q.sps, q.ilv) * q.mps * kStripCols;
-#pragma unroll
-        for (int c = 0; c < kWaveRows / 8; ++c) r.a[c] = ldg2<false>(src + wa + offa[c]);
-#pragma unroll
-        for (int c = 0; c < kWaveRows / 8; ++c) r.b[c] = ldg2<false>(src + wb + offb[c]);
+        const int s = fgram_strip(q, w, i);
+        fgram_fetch(q, w, s, r.a, r.b);
         const size_t col = (size_t)s * kStripCols + lq;
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
@@ -113,10 +68,10 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram(FGramArgs q) {
     FGramRegs pre;
     fetch(0, pre);
 #pragma unroll 1
-    for (int i = 0; i < tg; ++i) {
+    for (int i = 0; i < w.tg; ++i) {
         // the point's weights as the SM_PRODUCT form of the strip kernels makes them; columns beyond n weigh nothing (the
         // padding of x' is zero: the exponential there is finite)
-        const size_t col0 = (size_t)(v * q.sps + g + q.gs * i) * kStripCols + lq;
+        const size_t col0 = (size_t)fgram_strip(q, w, i) * kStripCols + lq;
         double u1[4], u2[4];
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
@@ -134,7 +89,7 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram(FGramArgs q) {
                 ac[qq][h] = ((qq & 1) ? av.y : av.x) - ca[h];
                 bc[qq][h] = ((qq & 1) ? bv.y : bv.x) - cb[h];
             }
-        fetch(i + 1 < tg ? i + 1 : i, pre);         // unconditional
+        fetch(i + 1 < w.tg ? i + 1 : i, pre);         // unconditional
         asm volatile("" ::: "memory");              // the loads are issued HERE, in front of the products (the compiler sank them behind)
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
@@ -159,7 +114,7 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram(FGramArgs q) {
     // The set leaves, accumulator by accumulator as the registers hold it: result register r of lane 16 lq + lr is row
     // 4 r + lq, column lr of the 16 x 16 block.  Row blocks beyond the strip's last one were redirected to the slice's first
     // (strip_chunk_offsets): what they leave lies beyond row m of the matrices and is never read (k_fgram_finish).
-    double* const dst = q.partial + (size_t)set * q.set_stride + (size_t)fgram_sub(si, sj) * kFGramSubDoubles + lane;
+    double* const dst = q.partial + (size_t)w.set * q.set_stride + (size_t)fgram_sub(w.si, w.sj) * kFGramSubDoubles + lane;
 #pragma unroll
     for (int h = 0; h < 4; ++h)
 #pragma unroll
@@ -169,16 +124,7 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram(FGramArgs q) {
                 dst[((0 * 16 + h * 4 + gb) * 4 + r) * 64] = acc1[h][gb][r];
                 dst[((1 * 16 + h * 4 + gb) * 4 + r) * 64] = acc2[h][gb][r];
             }
-    if (sj == 0) {                                  // (wave-uniform) the slices' row sums: one writer per slice and set
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            double t = rs[h];
-            t += __shfl_xor(t, 16, 64);
-            t += __shfl_xor(t, 32, 64);
-            const int row = ra + 16 * h + lr;
-            if (lq == 0) q.partial[(size_t)set * q.set_stride + q.rows_at + row] = row < q.mps ? t : 0.0;
-        }
-    }
+    fgram_store_row_sums(q, w, lq, lr, rs);
 }
 
 // out[e] = sum over segments (in index order) of [ the segment's gs sets added in turn ], e < count: on the sets' own
@@ -283,7 +229,7 @@ void launch_fgram_tail(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, c
 void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
                         const double* qv, const double* ybar, double theta) {
     hipLaunchKernelGGL(k_forces_gram, dim3(fgram_blocks(p)), dim3(256), 0, c->stream,
-                       fgram_args<FGramArgs>(c, p, buf, x, pscal, qv));
+                       fgram_args(c, p, buf, x, pscal, qv));
     launch_fgram_tail(c, p, buf, ybar, theta);
 }
 

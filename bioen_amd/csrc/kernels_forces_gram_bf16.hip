@@ -12,35 +12,14 @@
 // 64 x 64 sub-tile of both matrices (2 x 16 accumulators of 4 floats), a block of four waves a 128 x 128 tile pair I >= J, as
 // in k_forces_gram.  A set's f32 sums leave as doubles on k_forces_gram's layout, so the sets are added IN FP64 in its
 // fixed order by its k_fgram_sum_sets, and k_fgram_finish / k_fgram_square finish them: launch_fgram_tail, that file's,
-// launches those three kernels as they are.
-#include "strip.hpp"
+// launches those three kernels as they are.  What a wave does around its arithmetic is fgram.hpp's, shared with that kernel.
+#include "fgram.hpp"
 
 namespace bioen {
 
 typedef float fl4 __attribute__((ext_vector_type(4)));
 typedef short bh4 __attribute__((ext_vector_type(4)));      // four bfloat16: an operand fragment of the 16-deep instruction
 typedef unsigned u2v __attribute__((ext_vector_type(2)));   // the same two registers as they are filled: elements (0, 1) | (2, 3)
-
-constexpr int kFGram16SubDoubles = 2 * 16 * 4 * 64;     // = kFGramSubDoubles: [matrix 2][h 4][g 4][register 4][lane 64]
-
-struct FGram16Args {
-    const double* Ys;       // row-sum order strip copy
-    const double* center;   // mp values
-    int mps, mp, n;
-    int sps, gs, ilv;       // strips per segment, groups per segment, interleave of the copy
-    int nsets;              // local segments x gs
-    int nsl, ntiles;        // 64-row slices; 128-row tile pairs I >= J
-    const double* w0;       // the point: prior, x', q - qbar, scalar slot (S_LOGS)
-    const double* x;
-    const double* qv;
-    const double* pscal;
-    double* partial;        // ForcesGramPlan's sets
-    size_t set_stride;
-    size_t rows_at;
-};
-
-__host__ __device__ inline int fgram16_sub(int si, int sj) { return si * (si + 1) / 2 + sj; }
-
 typedef __bf16 bfp __attribute__((ext_vector_type(2)));
 typedef float flp __attribute__((ext_vector_type(2)));
 
@@ -66,41 +45,19 @@ struct FGram16Regs {
     double w0, x, qv;                // the strip's column lane & 15: a lane forms the weights of ONE column, the others arrive by shuffles
 };
 
-__global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGram16Args q) {
+__global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGramArgs q) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lq = lane >> 4, lr = lane & 15;
-    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
-    const int set = (k / q.ntiles) * 8 + xcd;
-    if (set >= q.nsets) return;
-    int ti = 0, tj = k % q.ntiles;
-    while (tj > ti) tj -= ++ti;                     // tile pair (ti, tj), tj <= ti
-    const int si = 2 * ti + (wave >> 1), sj = 2 * tj + (wave & 1);
-    if (si >= q.nsl || sj > si) return;             // (no barrier in this kernel: a wave may leave)
-    const int v = set / q.gs, g = set - v * q.gs;
-    const int tg = (q.sps - g + q.gs - 1) / q.gs;   // strips of the set (g < gs <= sps: at least one)
-    const int ra = si * kWaveRows, rb = sj * kWaveRows;
-    int offa[kWaveRows / 8], offb[kWaveRows / 8];
-    strip_chunk_offsets(q.mps, ra, offa);
-    strip_chunk_offsets(q.mps, rb, offb);
-    const size_t wa = (size_t)ra * kStripCols + (size_t)lane * 2, wb = (size_t)rb * kStripCols + (size_t)lane * 2;
+    FGramWave w;
+    if (!fgram_decode(q, lane, wave, w)) return;
     const double logs = q.pscal[S_LOGS];
-
     double ca[4], cb[4];                            // the centres of the lane's rows
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        const int rowa = ra + 16 * h + lr, rowb = rb + 16 * h + lr;
-        ca[h] = rowa < q.mp ? q.center[rowa] : 0.0;
-        cb[h] = rowb < q.mp ? q.center[rowb] : 0.0;
-    }
+    fgram_centres(q, w, lr, ca, cb);
 
     auto fetch = [&](int i, FGram16Regs& r) {
-        const int s = v * q.sps + g + q.gs * i;
-        const double* src = q.Ys + (size_t)strip_phys(s, q.sps, q.ilv) * q.mps * kStripCols;
-#pragma unroll
-        for (int c = 0; c < kWaveRows / 8; ++c) r.a[c] = ldg2<false>(src + wa + offa[c]);
-#pragma unroll
-        for (int c = 0; c < kWaveRows / 8; ++c) r.b[c] = ldg2<false>(src + wb + offb[c]);
+        const int s = fgram_strip(q, w, i);
+        fgram_fetch(q, w, s, r.a, r.b);
         const size_t col = (size_t)s * kStripCols + lr;
         r.w0 = q.w0[col];
         r.x = q.x[col];
@@ -124,10 +81,10 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGram16Args q) {
     FGram16Regs pre;
     fetch(0, pre);
 #pragma unroll 1
-    for (int i = 0; i < tg; ++i) {
+    for (int i = 0; i < w.tg; ++i) {
         // the point's weights as k_forces_gram forms them (the same operations, so the same bits), columns beyond n weigh
         // nothing -- formed once per column (lane & 15) and handed to the lanes that multiply with them: 4 qq + lq
-        const size_t colc = (size_t)(v * q.sps + g + q.gs * i) * kStripCols + lr;
+        const size_t colc = (size_t)fgram_strip(q, w, i) * kStripCols + lr;
         const double e = exp(pre.x - logs);
         const double u1c = colc < (size_t)q.n ? pre.w0 * e : 0.0;
         const double u2c = u1c * pre.qv;
@@ -158,7 +115,7 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGram16Args q) {
                 b2h[h][qp] = hi;
                 b2l[h][qp] = lo;
             }
-        fetch(i + 1 < tg ? i + 1 : i, pre);         // unconditional
+        fetch(i + 1 < w.tg ? i + 1 : i, pre);         // unconditional
         asm volatile("" ::: "memory");              // the loads are issued HERE, in front of the products
 #pragma unroll
         for (int h = 0; h < 4; ++h)
@@ -177,7 +134,7 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGram16Args q) {
     // (i & 15) >> 2 of lane 16 (i & 3) + j).  Result register r of lane 16 lq + lr of THIS instruction is row 4 lq + r,
     // column lr of the block: it goes to register slot lq, lane 16 r + lr.  Row blocks beyond the strip's last one were
     // redirected (strip_chunk_offsets): what they leave lies beyond row m and is never read (k_fgram_finish).
-    double* const dst = q.partial + (size_t)set * q.set_stride + (size_t)fgram16_sub(si, sj) * kFGram16SubDoubles + lr;
+    double* const dst = q.partial + (size_t)w.set * q.set_stride + (size_t)fgram_sub(w.si, w.sj) * kFGramSubDoubles + lr;
 #pragma unroll
     for (int h = 0; h < 4; ++h)
 #pragma unroll
@@ -187,16 +144,7 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGram16Args q) {
                 dst[((0 * 16 + h * 4 + gb) * 4 + lq) * 64 + 16 * r] = (double)acc1[h][gb][r];
                 dst[((1 * 16 + h * 4 + gb) * 4 + lq) * 64 + 16 * r] = (double)acc2[h][gb][r];
             }
-    if (sj == 0) {                                  // (wave-uniform) the slices' row sums: one writer per slice and set
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            double t = rs[h];
-            t += __shfl_xor(t, 16, 64);
-            t += __shfl_xor(t, 32, 64);
-            const int row = ra + 16 * h + lr;
-            if (lq == 0) q.partial[(size_t)set * q.set_stride + q.rows_at + row] = row < q.mps ? t : 0.0;
-        }
-    }
+    fgram_store_row_sums(q, w, lq, lr, rs);
 }
 
 // ---- host side ------------------------------------------------------------------------------------
@@ -205,7 +153,7 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGram16Args q) {
 void launch_forces_gram_bf16(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
                              const double* qv, const double* ybar, double theta) {
     hipLaunchKernelGGL(k_forces_gram_bf16, dim3(fgram_blocks(p)), dim3(256), 0, c->stream,
-                       fgram_args<FGram16Args>(c, p, buf, x, pscal, qv));
+                       fgram_args(c, p, buf, x, pscal, qv));
     launch_fgram_tail(c, p, buf, ybar, theta);
 }
 

@@ -10,78 +10,37 @@
 //   k_flaplace_trmm        B = W C, tile (i, j) sums over k <= i
 //   k_flaplace_to_colquad  H^-1 as k_forces_colquad takes its P_eff (padded to the strip rows, scaled by s_i s_j), and the
 //                          diagonals of both covariances
-// Every tile product runs on v_mfma_f64_16x16x4_f64 with k_fnewton_syrk's operand and result layouts.  No cooperative
+// Every tile product is tile64.hpp's (v_mfma_f64_16x16x4_f64; k_fnewton_syrk runs the same one).  No cooperative
 // launch, no grid-wide wait, no atomics: every element has one writer per launch, and every sum runs over the tiles and
 // their inner index in ascending order -- its shape is a function of m alone, so the same bits in give the same bits out.
 // Every index is held against m: rows and columns m .. of a padded buffer are never read as data (they enter as zeros).
-#include "kernels.hpp"
+#include "tile64.hpp"
 
 namespace bioen {
-
-typedef double d4l __attribute__((ext_vector_type(4)));
-
-constexpr int kLT = kFNewtonPanel;      // a tile's rows and columns
-
-// 32 inner columns (half = 0, 1) of a 64 x 64 operand tile into dst[row][inner].  ROWS: element (r, k) of the tile is
-// X[r0 + r][k0 + k] (a wave-load is two runs of 256 bytes); else it is X[k0 + k][r0 + r], the tile of X^T (one run of 512).
-template <bool ROWS>
-__device__ __forceinline__ void flap_stage(double (*dst)[33], const double* X, int ld, int m, int r0, int k0, int half) {
-#pragma unroll
-    for (int it = 0; it < kLT * 32 / 256; ++it) {
-        const int e = threadIdx.x + 256 * it;
-        const int r = ROWS ? e >> 5 : e & 63, k = ROWS ? e & 31 : e >> 6;
-        const int gr = r0 + r, gk = k0 + 32 * half + k;
-        dst[r][k] = (gr < m && gk < m) ? X[ROWS ? (size_t)gr * ld + gk : (size_t)gk * ld + gr] : 0.0;
-    }
-}
-
-// acc += the 64 inner columns staged in two halves: wave w the tile's rows 16 w .. 16 w + 15 against its four column blocks
-__device__ __forceinline__ void flap_mfma(d4l acc[4], const double (*as)[33], const double (*bs)[33], int wave, int lq, int lr) {
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        const double av = as[16 * wave + lr][4 * s + lq];
-#pragma unroll
-        for (int gb = 0; gb < 4; ++gb) acc[gb] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bs[16 * gb + lr][4 * s + lq], acc[gb], 0, 0, 0);
-    }
-}
-
-// acc[r][c] += sum_k a(r, k) b(c, k) over one 64 x 64 x 64 tile product, inner index ascending
-template <bool AROWS, bool BROWS>
-__device__ __forceinline__ void flap_tile(d4l acc[4], double (*as)[33], double (*bs)[33], const double* A, int lda, int ar0, int ak0,
-                                          const double* B, int ldb, int br0, int bk0, int m) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int half = 0; half < 2; ++half) {
-        __syncthreads();                                     // the product before has read its operands
-        flap_stage<AROWS>(as, A, lda, m, ar0, ak0, half);
-        flap_stage<BROWS>(bs, B, ldb, m, br0, bk0, half);
-        __syncthreads();
-        flap_mfma(acc, as, bs, wave, lane >> 4, lane & 15);
-    }
-}
 
 // The diagonal tile at k0 = 64 blockIdx.x (nb = min(64, m - k0) rows): lane c owns column c of X = L11^-1, X L11^T = I
 // column by column as k_fnewton_trsm solves its rows (the unit matrix's rows for the panel's).  Rows and columns >= nb
 // are the identity's.  One reciprocal per pivot.  ldiag <- the diagonal of L.
 __global__ __launch_bounds__(64) void k_flaplace_tinv(const double* __restrict__ L, int ldl, int m, double* __restrict__ W, int ldw,
                                                      double* __restrict__ ldiag) {
-    __shared__ double dinv[kLT];
-    __shared__ double tt[kLT][kLT + 2];                      // L11 transposed: tt[j][t] = L11[t][j]
-    const int k0 = blockIdx.x * kLT;
-    const int nb = min(kLT, m - k0);
+    __shared__ double dinv[kT64];
+    __shared__ double tt[kT64][kT64 + 2];                      // L11 transposed: tt[j][t] = L11[t][j]
+    const int k0 = blockIdx.x * kT64;
+    const int nb = min(kT64, m - k0);
     const int c = threadIdx.x;
-    for (int r = 0; r < kLT; ++r)                            // row r of the tile, one element per lane
+    for (int r = 0; r < kT64; ++r)                            // row r of the tile, one element per lane
         tt[c][r] = (r < nb && c <= r) ? L[(size_t)(k0 + r) * ldl + k0 + c] : (r == c ? 1.0 : 0.0);
     __syncthreads();
     const double dgc = tt[c][c];
     dinv[c] = 1.0 / dgc;
     if (c < nb) ldiag[k0 + c] = dgc;
     __syncthreads();
-    double a[kLT];
+    double a[kT64];
 #pragma unroll
-    for (int t = 0; t < kLT; ++t) a[t] = t == c ? 1.0 : 0.0;
+    for (int t = 0; t < kT64; ++t) a[t] = t == c ? 1.0 : 0.0;
     int z = 0;
 #pragma unroll
-    for (int j = 0; j < kLT; ++j) {
+    for (int j = 0; j < kT64; ++j) {
         const double x = a[j] * dinv[j];
         a[j] = x;
         // (as in k_fnewton_trsm: the column's address passes through a register the compiler cannot see through, or it
@@ -89,10 +48,10 @@ __global__ __launch_bounds__(64) void k_flaplace_tinv(const double* __restrict__
         asm volatile("" : "+v"(z) : "v"(x));
         const double* const col = &tt[j][0] + z;
 #pragma unroll
-        for (int t = j + 1; t < kLT; ++t) a[t] = fma(-x, col[t], a[t]);
+        for (int t = j + 1; t < kT64; ++t) a[t] = fma(-x, col[t], a[t]);
     }
 #pragma unroll
-    for (int t = 0; t < kLT; ++t)
+    for (int t = 0; t < kT64; ++t)
         if (t < nb && c < nb) W[(size_t)(k0 + t) * ldw + k0 + c] = a[t];      // a[t] = X[t][c]: zero above the diagonal
 }
 
@@ -100,17 +59,17 @@ __global__ __launch_bounds__(64) void k_flaplace_tinv(const double* __restrict__
 // D_i = W_ii.  The W_kj are of distances 0 .. d - 1: written by the launches before.  The sum leaves the registers through
 // LDS as the second product's B operand, half by half.
 __global__ __launch_bounds__(256) void k_flaplace_trtri(const double* __restrict__ L, int ldl, double* W, int ldw, int m, int d) {
-    __shared__ double as[kLT][33], bs[kLT][33];
+    __shared__ double as[kT64][33], bs[kT64][33];
     const int tj = blockIdx.x, ti = tj + d;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lq = lane >> 4, lr = lane & 15;
-    d4l acc[4], out[4];
+    d4 acc[4], out[4];
 #pragma unroll
-    for (int gb = 0; gb < 4; ++gb) acc[gb] = out[gb] = d4l{0.0, 0.0, 0.0, 0.0};
-    for (int k = tj; k < ti; ++k) flap_tile<true, false>(acc, as, bs, L, ldl, ti * kLT, k * kLT, W, ldw, tj * kLT, k * kLT, m);
+    for (int gb = 0; gb < 4; ++gb) acc[gb] = out[gb] = d4{0.0, 0.0, 0.0, 0.0};
+    for (int k = tj; k < ti; ++k) t64_tile<true, false>(acc, as, bs, L, ldl, ti * kT64, k * kT64, W, ldw, tj * kT64, k * kT64, m);
     for (int half = 0; half < 2; ++half) {
         __syncthreads();
-        flap_stage<true>(as, W, ldw, m, ti * kLT, ti * kLT, half);
+        t64_stage<true>(as, W, ldw, m, ti * kT64, ti * kT64, half);
         if ((wave >> 1) == half) {                           // the sum's rows 32 half .. 32 half + 31 are these two waves'
 #pragma unroll
             for (int gb = 0; gb < 4; ++gb)
@@ -118,13 +77,13 @@ __global__ __launch_bounds__(256) void k_flaplace_trtri(const double* __restrict
                 for (int r = 0; r < 4; ++r) bs[16 * gb + lr][16 * (wave & 1) + 4 * r + lq] = acc[gb][r];
         }
         __syncthreads();
-        flap_mfma(out, as, bs, wave, lq, lr);
+        t64_mfma(out, as, bs, wave, lq, lr);
     }
 #pragma unroll
     for (int gb = 0; gb < 4; ++gb)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int i = ti * kLT + 16 * wave + 4 * r + lq, j = tj * kLT + 16 * gb + lr;
+            const int i = ti * kT64 + 16 * wave + 4 * r + lq, j = tj * kT64 + 16 * gb + lr;
             if (i < m && j < m) W[(size_t)i * ldw + j] = -out[gb][r];
         }
 }
@@ -134,21 +93,21 @@ __global__ __launch_bounds__(256) void k_flaplace_trtri(const double* __restrict
 // one register; in a diagonal tile the entries right of the diagonal are the mirrors of those left of it.
 __global__ __launch_bounds__(256) void k_flaplace_ata(const double* __restrict__ X, int ldx, double* __restrict__ S, int lds, int m,
                                                      int lower) {
-    __shared__ double as[kLT][33], bs[kLT][33];
-    int ti = 0, tj = blockIdx.x;
-    while (tj > ti) tj -= ++ti;
-    const int nt = (m + kLT - 1) / kLT;
+    __shared__ double as[kT64][33], bs[kT64][33];
+    int ti, tj;
+    tile_pair(blockIdx.x, ti, tj);
+    const int nt = (m + kT64 - 1) / kT64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lq = lane >> 4, lr = lane & 15;
-    d4l acc[4];
+    d4 acc[4];
 #pragma unroll
-    for (int gb = 0; gb < 4; ++gb) acc[gb] = d4l{0.0, 0.0, 0.0, 0.0};
-    for (int k = lower ? ti : 0; k < nt; ++k) flap_tile<false, false>(acc, as, bs, X, ldx, ti * kLT, k * kLT, X, ldx, tj * kLT, k * kLT, m);
+    for (int gb = 0; gb < 4; ++gb) acc[gb] = d4{0.0, 0.0, 0.0, 0.0};
+    for (int k = lower ? ti : 0; k < nt; ++k) t64_tile<false, false>(acc, as, bs, X, ldx, ti * kT64, k * kT64, X, ldx, tj * kT64, k * kT64, m);
 #pragma unroll
     for (int gb = 0; gb < 4; ++gb)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int i = ti * kLT + 16 * wave + 4 * r + lq, j = tj * kLT + 16 * gb + lr;
+            const int i = ti * kT64 + 16 * wave + 4 * r + lq, j = tj * kT64 + 16 * gb + lr;
             if (i < m && j <= i) {
                 S[(size_t)i * lds + j] = acc[gb][r];
                 if (j < i) S[(size_t)j * lds + i] = acc[gb][r];
@@ -160,19 +119,19 @@ __global__ __launch_bounds__(256) void k_flaplace_ata(const double* __restrict__
 // blockIdx.x) over k = 0 .. i
 __global__ __launch_bounds__(256) void k_flaplace_trmm(const double* __restrict__ W, int ldw, const double* __restrict__ Cm, int ldc,
                                                       double* __restrict__ B, int ldb, int m) {
-    __shared__ double as[kLT][33], bs[kLT][33];
+    __shared__ double as[kT64][33], bs[kT64][33];
     const int ti = blockIdx.y, tj = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lq = lane >> 4, lr = lane & 15;
-    d4l acc[4];
+    d4 acc[4];
 #pragma unroll
-    for (int gb = 0; gb < 4; ++gb) acc[gb] = d4l{0.0, 0.0, 0.0, 0.0};
-    for (int k = 0; k <= ti; ++k) flap_tile<true, true>(acc, as, bs, W, ldw, ti * kLT, k * kLT, Cm, ldc, tj * kLT, k * kLT, m);
+    for (int gb = 0; gb < 4; ++gb) acc[gb] = d4{0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k <= ti; ++k) t64_tile<true, true>(acc, as, bs, W, ldw, ti * kT64, k * kT64, Cm, ldc, tj * kT64, k * kT64, m);
 #pragma unroll
     for (int gb = 0; gb < 4; ++gb)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int i = ti * kLT + 16 * wave + 4 * r + lq, j = tj * kLT + 16 * gb + lr;
+            const int i = ti * kT64 + 16 * wave + 4 * r + lq, j = tj * kT64 + 16 * gb + lr;
             if (i < m && j < m) B[(size_t)i * ldb + j] = acc[gb][r];
         }
 }
@@ -199,7 +158,7 @@ __global__ __launch_bounds__(256) void k_flaplace_to_colquad(const double* __res
 // ---- host side ------------------------------------------------------------------------------------
 // W (ldw x ldw) <- L^-1, Hi (m x m, dense) <- W^T W, ldiag <- diag L.  1 + (T - 1) + 1 launches.  Enqueues only.
 void launch_flaplace_inverse(bioen_hip_ctx* c, const double* L, int ldl, double* W, int ldw, double* Hi, double* ldiag) {
-    const int m = c->m, nt = (m + kLT - 1) / kLT;
+    const int m = c->m, nt = (m + kT64 - 1) / kT64;
     hipLaunchKernelGGL(k_flaplace_tinv, dim3(nt), dim3(64), 0, c->stream, L, ldl, m, W, ldw, ldiag);
     for (int d = 1; d < nt; ++d) hipLaunchKernelGGL(k_flaplace_trtri, dim3(nt - d), dim3(256), 0, c->stream, L, ldl, W, ldw, m, d);
     hipLaunchKernelGGL(k_flaplace_ata, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, W, ldw, Hi, m, m, 1);
@@ -207,7 +166,7 @@ void launch_flaplace_inverse(bioen_hip_ctx* c, const double* L, int ldl, double*
 
 // B (ldb x ldb) <- W Cm, Ca (m x m, dense) <- B^T B; Cm: m x m, dense, symmetric
 void launch_flaplace_averages(bioen_hip_ctx* c, const double* W, int ldw, const double* Cm, double* B, int ldb, double* Ca) {
-    const int m = c->m, nt = (m + kLT - 1) / kLT;
+    const int m = c->m, nt = (m + kT64 - 1) / kT64;
     hipLaunchKernelGGL(k_flaplace_trmm, dim3(nt, nt), dim3(256), 0, c->stream, W, ldw, Cm, m, B, ldb, m);
     hipLaunchKernelGGL(k_flaplace_ata, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, B, ldb, Ca, m, m, 0);
 }

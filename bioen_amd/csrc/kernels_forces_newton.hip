@@ -5,6 +5,7 @@
 //   k_fnewton_trsm    one wave (of a block's four, which fetch L11 together) per 64 rows below the tile: lane i owns row i of  X L11^T = A21, L11 read from LDS
 //   k_fnewton_syrk    the trailing lower triangle  A22 -= L21 L21^T  in 64 x 64 tiles on v_mfma_f64_16x16x4_f64 -- the only
 //                     place the M^3 / 3 flops are
+// The tile product is tile64.hpp's, shared with the inversion (kernels_forces_laplace.hip).
 // No cooperative launch, no grid-wide wait, no atomics: every element has one writer per launch, and every sum runs over
 // the panel's columns in index order -- its shape is a function of m alone, so two factorisations of the same bits give
 // the same bits.  Only the lower triangle of the source is ever read; rows and columns m .. mp of the padded buffer are
@@ -16,11 +17,9 @@
 // k_fnewton_solve: one block, L y = b then L^T x = y for k <= 8 right-hand sides; a diagonal tile is solved by one wave
 // per right-hand side (lane t owns unknown t, L11 in LDS), the rest are GEMV updates: forward a wave per 32 rows with a
 // butterfly sum (coalesced row segments), backward one column per thread.  A right-hand side's arithmetic does not depend on k: a column of a batch is the single solve.
-#include "kernels.hpp"
+#include "tile64.hpp"
 
 namespace bioen {
-
-typedef double d4n __attribute__((ext_vector_type(4)));
 
 // lane `src`'s value in every lane, src wave-uniform: two scalar lane reads, no trip through LDS as __shfl takes (the
 // substitutions below are chains of these)
@@ -29,9 +28,6 @@ __device__ __forceinline__ double fnewton_lane(double v, int src) {
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
     return __hiloint2double(hi, lo);
 }
-
-constexpr int kNB = kFNewtonPanel;
-constexpr int kNBPad = kNB + 1;
 
 // L <- the lower triangle of src (m x m, row-major, leading dimension lds) + lambda I, zeros above the diagonal; dg <-
 // the diagonal of src (without lambda); *info <- 0.  Reads nothing above the diagonal.
@@ -56,17 +52,17 @@ __global__ __launch_bounds__(256) void k_fnewton_load(const double* __restrict__
 // the rest of its row.  Rows >= nb are rows of the identity.  Entries right of a lane's diagonal are never loaded (zero)
 // and what the updates leave there is never stored.
 __global__ __launch_bounds__(64) void k_fnewton_potrf(double* __restrict__ L, int ldl, int m, int k0, int* __restrict__ info) {
-    __shared__ double col[2][kNB];
+    __shared__ double col[2][kT64];
     if (*info != 0) return;
     const int i = threadIdx.x;
-    const int nb = min(kNB, m - k0);
-    double a[kNB];
+    const int nb = min(kT64, m - k0);
+    double a[kT64];
     double* const row = L + (size_t)(k0 + i) * ldl + k0;
 #pragma unroll
-    for (int t = 0; t < kNB; ++t) a[t] = (i < nb && t <= i) ? row[t] : (t == i ? 1.0 : 0.0);
+    for (int t = 0; t < kT64; ++t) a[t] = (i < nb && t <= i) ? row[t] : (t == i ? 1.0 : 0.0);
     int bad = 0;
 #pragma unroll
-    for (int j = 0; j < kNB; ++j) {
+    for (int j = 0; j < kT64; ++j) {
         const double p = fnewton_lane(a[j], j);                // the pivot, as lane j holds it
         if (!(p > 0.0) || !(p <= 1.7976931348623157e308)) {  // <= 0, NaN or infinite (wave-uniform)
             bad = j + 1;
@@ -78,7 +74,7 @@ __global__ __launch_bounds__(64) void k_fnewton_potrf(double* __restrict__ L, in
         col[j & 1][i] = l;
         __syncthreads();
 #pragma unroll
-        for (int t = j + 1; t < kNB; ++t) a[t] = fma(-l, col[j & 1][t], a[t]);
+        for (int t = j + 1; t < kT64; ++t) a[t] = fma(-l, col[j & 1][t], a[t]);
     }
     if (bad) {
         if (i == 0) *info = k0 + bad;
@@ -86,7 +82,7 @@ __global__ __launch_bounds__(64) void k_fnewton_potrf(double* __restrict__ L, in
     }
     if (i < nb) {
 #pragma unroll
-        for (int t = 0; t < kNB; ++t)
+        for (int t = 0; t < kT64; ++t)
             if (t <= i) row[t] = a[t];
     }
 }
@@ -94,31 +90,31 @@ __global__ __launch_bounds__(64) void k_fnewton_potrf(double* __restrict__ L, in
 // The panel below the tile: rows k0 + nb + 64 b + i, lane i owns one; X L11^T = A21 column by column, the multiples of a
 // found entry taken off the rest of the row at once (independent fmas).  Columns >= nb of L11 are the identity's.
 __global__ __launch_bounds__(256) void k_fnewton_trsm(double* __restrict__ L, int ldl, int m, int k0, const int* __restrict__ info) {
-    __shared__ double dinv[kNB];
-    __shared__ double tt[kNB][kNB + 2];                      // L11 transposed: a column of L11 is read as one row (every lane the same address)
+    __shared__ double dinv[kT64];
+    __shared__ double tt[kT64][kT64 + 2];                      // L11 transposed: a column of L11 is read as one row (every lane the same address)
     if (*info != 0) return;
-    const int nb = min(kNB, m - k0);
+    const int nb = min(kT64, m - k0);
     // four waves fetch the tile (16 independent loads per thread); the first solves
 #pragma unroll
-    for (int it = 0; it < kNB * kNB / 256; ++it) {
+    for (int it = 0; it < kT64 * kT64 / 256; ++it) {
         const int e = threadIdx.x + 256 * it;
-        const int r = e / kNB, s = e % kNB;
+        const int r = e / kT64, s = e % kT64;
         tt[s][r] = (r < nb && s <= r) ? L[(size_t)(k0 + r) * ldl + k0 + s] : (r == s ? 1.0 : 0.0);
     }
     __syncthreads();
-    if (threadIdx.x < kNB) dinv[threadIdx.x] = 1.0 / tt[threadIdx.x][threadIdx.x];      // one division per column, not one per row and column
+    if (threadIdx.x < kT64) dinv[threadIdx.x] = 1.0 / tt[threadIdx.x][threadIdx.x];      // one division per column, not one per row and column
     __syncthreads();
-    if (threadIdx.x >= kNB) return;
+    if (threadIdx.x >= kT64) return;
     const int i = threadIdx.x;
-    const int r = k0 + nb + blockIdx.x * kNB + i;
+    const int r = k0 + nb + blockIdx.x * kT64 + i;
     const bool live = r < m;
     double* const row = L + (size_t)(live ? r : 0) * ldl + k0;
-    double a[kNB];
+    double a[kT64];
 #pragma unroll
-    for (int t = 0; t < kNB; ++t) a[t] = (live && t < nb) ? row[t] : 0.0;
+    for (int t = 0; t < kT64; ++t) a[t] = (live && t < nb) ? row[t] : 0.0;
     int z = 0;
 #pragma unroll
-    for (int j = 0; j < kNB; ++j) {
+    for (int j = 0; j < kT64; ++j) {
         const double x = a[j] * dinv[j];
         a[j] = x;
         // column j of L11 is read HERE, behind x: its address passes through a register the compiler cannot see through
@@ -126,49 +122,28 @@ __global__ __launch_bounds__(256) void k_fnewton_trsm(double* __restrict__ L, in
         asm volatile("" : "+v"(z) : "v"(x));
         const double* const c = &tt[j][0] + z;
 #pragma unroll
-        for (int t = j + 1; t < kNB; ++t) a[t] = fma(-x, c[t], a[t]);
+        for (int t = j + 1; t < kT64; ++t) a[t] = fma(-x, c[t], a[t]);
     }
 #pragma unroll
-    for (int t = 0; t < kNB; ++t)
+    for (int t = 0; t < kT64; ++t)
         if (live && t < nb) row[t] = a[t];
 }
 
-// A22 -= L21 L21^T on the lower triangle, 64 x 64 tiles (ti >= tj), four waves, wave w the tile's rows 16 w .. 16 w + 15
-// against its four column blocks: 4 accumulators of v_mfma_f64_16x16x4_f64 (A and B operand: row = lane & 15, k = lane >>
-// 4; result register r of lane 16 q + c: row 4 r + q, column c -- the layouts of k_forces_gram).  The two operand blocks
-// pass through LDS in two halves of 32 panel columns; the inner index runs 0 .. nb - 1 in order (columns >= nb are zeros).
+// A22 -= L21 L21^T on the lower triangle, 64 x 64 tiles (ti >= tj), four waves: one tile product (tile64.hpp) over the
+// panel's columns, the inner index 0 .. nb - 1 in order (columns >= nb are zeros).
 __global__ __launch_bounds__(256) void k_fnewton_syrk(double* __restrict__ L, int ldl, int m, int k0, const int* __restrict__ info) {
-    __shared__ double as[kNB][33], bs[kNB][33];
+    __shared__ double as[kT64][33], bs[kT64][33];
     if (*info != 0) return;
-    const int nb = min(kNB, m - k0);
-    const int base = k0 + nb;                                // first trailing row
-    int ti = 0, tj = blockIdx.x;
-    while (tj > ti) tj -= ++ti;                              // tile pair (ti, tj), tj <= ti
-    const int r0 = base + ti * kNB, c0 = base + tj * kNB;
+    const int base = k0 + min(kT64, m - k0);                  // first trailing row
+    int ti, tj;
+    tile_pair(blockIdx.x, ti, tj);
+    const int r0 = base + ti * kT64, c0 = base + tj * kT64;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lq = lane >> 4, lr = lane & 15;
-    d4n acc[4];
+    d4 acc[4];
 #pragma unroll
-    for (int gb = 0; gb < 4; ++gb) acc[gb] = d4n{0.0, 0.0, 0.0, 0.0};
-    for (int half = 0; half < 2; ++half) {
-        if (half) __syncthreads();
-#pragma unroll
-        for (int it = 0; it < kNB * 32 / 256; ++it) {        // (a fixed count, unrolled: the 16 loads of a thread travel together)
-            const int e = threadIdx.x + 256 * it;
-            const int r = e >> 5, s = (e & 31) + 32 * half;
-            const bool ok = s < nb;
-            as[r][e & 31] = (ok && r0 + r < m) ? L[(size_t)(r0 + r) * ldl + k0 + s] : 0.0;
-            bs[r][e & 31] = (ok && c0 + r < m) ? L[(size_t)(c0 + r) * ldl + k0 + s] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const double av = as[16 * wave + lr][4 * s + lq];
-#pragma unroll
-            for (int gb = 0; gb < 4; ++gb)
-                acc[gb] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bs[16 * gb + lr][4 * s + lq], acc[gb], 0, 0, 0);
-        }
-    }
+    for (int gb = 0; gb < 4; ++gb) acc[gb] = d4{0.0, 0.0, 0.0, 0.0};
+    t64_tile<true, true>(acc, as, bs, L, ldl, r0, k0, L, ldl, c0, k0, m);
 #pragma unroll
     for (int gb = 0; gb < 4; ++gb)
 #pragma unroll
@@ -178,27 +153,33 @@ __global__ __launch_bounds__(256) void k_fnewton_syrk(double* __restrict__ L, in
         }
 }
 
+// The solve's diagonal tile at j0 (nb rows) into t11, the identity beyond nb, and dinv <- 1 / its diagonal: one division
+// per unknown, outside the chain.  1024 threads, four loads each; ends with a barrier.
+__device__ __forceinline__ void fnewton_solve_tile(double (*t11)[kT64 + 1], double* dinv, const double* L, int ldl, int j0, int nb) {
+#pragma unroll
+    for (int it = 0; it < kT64 * kT64 / 1024; ++it) {
+        const int e = threadIdx.x + 1024 * it;
+        const int r = e / kT64, s = e % kT64;
+        const double v = (r < nb && s <= r) ? L[(size_t)(j0 + r) * ldl + j0 + s] : (r == s ? 1.0 : 0.0);
+        t11[r][s] = v;
+        if (r == s) dinv[r] = 1.0 / v;
+    }
+    __syncthreads();
+}
+
 // X: [k][ldx], right-hand sides in, solutions out.  1024 threads; wave a < k solves the diagonal tiles of right-hand side a.
 __global__ __launch_bounds__(1024) void k_fnewton_solve(const double* __restrict__ L, int ldl, int m, int k, double* __restrict__ X,
                                                         int ldx) {
-    __shared__ double t11[kNB][kNBPad];
-    __shared__ double xs[kMaxBatch][kNB];
-    __shared__ double dinv[kNB];                             // 1 / diagonal of the tile: one division per unknown, outside the chain
+    __shared__ double t11[kT64][kT64 + 1];
+    __shared__ double xs[kMaxBatch][kT64];
+    __shared__ double dinv[kT64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int np = (m + kNB - 1) / kNB;
+    const int np = (m + kT64 - 1) / kT64;
     // ---- L y = b, panels first to last
     for (int p = 0; p < np; ++p) {
-        const int j0 = p * kNB, nb = min(kNB, m - j0);
+        const int j0 = p * kT64, nb = min(kT64, m - j0);
         __syncthreads();                                     // the updates of the panel before are in X; t11 and xs are free
-#pragma unroll
-        for (int it = 0; it < kNB * kNB / 1024; ++it) {
-            const int e = tid + 1024 * it;
-            const int r = e / kNB, s = e % kNB;
-            const double v = (r < nb && s <= r) ? L[(size_t)(j0 + r) * ldl + j0 + s] : (r == s ? 1.0 : 0.0);
-            t11[r][s] = v;
-            if (r == s) dinv[r] = 1.0 / v;
-        }
-        __syncthreads();
+        fnewton_solve_tile(t11, dinv, L, ldl, j0, nb);
         if (wave < k) {
             double v = lane < nb ? X[(size_t)wave * ldx + j0 + lane] : 0.0;
             for (int j = 0; j < nb; ++j) {
@@ -240,17 +221,9 @@ __global__ __launch_bounds__(1024) void k_fnewton_solve(const double* __restrict
     }
     // ---- L^T x = y, panels last to first
     for (int p = np - 1; p >= 0; --p) {
-        const int j0 = p * kNB, nb = min(kNB, m - j0);
+        const int j0 = p * kT64, nb = min(kT64, m - j0);
         __syncthreads();
-#pragma unroll
-        for (int it = 0; it < kNB * kNB / 1024; ++it) {
-            const int e = tid + 1024 * it;
-            const int r = e / kNB, s = e % kNB;
-            const double v = (r < nb && s <= r) ? L[(size_t)(j0 + r) * ldl + j0 + s] : (r == s ? 1.0 : 0.0);
-            t11[r][s] = v;
-            if (r == s) dinv[r] = 1.0 / v;
-        }
-        __syncthreads();
+        fnewton_solve_tile(t11, dinv, L, ldl, j0, nb);
         if (wave < k) {
             double v = lane < nb ? X[(size_t)wave * ldx + j0 + lane] : 0.0;
             for (int j = nb - 1; j >= 0; --j) {
@@ -268,7 +241,7 @@ __global__ __launch_bounds__(1024) void k_fnewton_solve(const double* __restrict
 #pragma unroll
             for (int a = 0; a < kMaxBatch; ++a) s[a] = 0.0;
 #pragma unroll 16
-            for (int t = 0; t < kNB; ++t) {
+            for (int t = 0; t < kT64; ++t) {
                 const double l = t < nb ? L[(size_t)(j0 + t) * ldl + i] : 0.0;
 #pragma unroll
                 for (int a = 0; a < kMaxBatch; ++a)
@@ -287,11 +260,11 @@ void launch_fnewton_factor(bioen_hip_ctx* c, const double* src, int lds, double 
     const int m = c->m;
     const int tb = (m + 15) / 16;
     hipLaunchKernelGGL(k_fnewton_load, dim3(tb, tb), dim3(256), 0, c->stream, src, lds, m, ldl, lambda, L, dg, info);
-    for (int k0 = 0; k0 < m; k0 += kNB) {
+    for (int k0 = 0; k0 < m; k0 += kT64) {
         hipLaunchKernelGGL(k_fnewton_potrf, dim3(1), dim3(64), 0, c->stream, L, ldl, m, k0, info);
-        const int below = m - k0 - kNB;
+        const int below = m - k0 - kT64;
         if (below <= 0) break;
-        const int nt = (below + kNB - 1) / kNB;
+        const int nt = (below + kT64 - 1) / kT64;
         hipLaunchKernelGGL(k_fnewton_trsm, dim3(nt), dim3(256), 0, c->stream, L, ldl, m, k0, info);
         hipLaunchKernelGGL(k_fnewton_syrk, dim3(nt * (nt + 1) / 2), dim3(256), 0, c->stream, L, ldl, m, k0, info);
     }

@@ -288,35 +288,6 @@ inline int strip_ilv(const bioen_hip_ctx* c) { return std::max(1, c->strip_ilv);
 inline int reduced_rows(const bioen_hip_ctx* c) { return (int)round_up((size_t)c->m, c->mp > 512 ? 2 * kWaveRows : kWaveRows); }
 bool one_copy_by_default(const bioen_hip_ctx* c);      // strip_plan.cpp
 
-// The dense Hessian passes (kernels_forces_gram.hip: FGramArgs, kernels_forces_gram_bf16.hip: FGram16Args): what the two
-// kernels' arguments have in common, which is every field -- the copy, the plan's sets in buf, the kept point -- and
-// their grid: a tile pair per set, the tiles of one set on one XCD
-template <class Args>
-Args fgram_args(const bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
-                const double* qv) {
-    Args q{};
-    q.Ys = c->Ys[0];
-    q.center = c->strip_center;
-    q.mps = panel_mps(c, 0);
-    q.mp = c->mp;
-    q.n = c->n;
-    q.sps = strip_sps(c);
-    q.gs = p.gs;
-    q.ilv = strip_ilv(c);
-    q.nsets = p.nsets;
-    q.nsl = p.nsl;
-    q.ntiles = p.ntiles;
-    q.w0 = c->fixed;
-    q.x = x;
-    q.qv = qv;
-    q.pscal = pscal;
-    q.partial = buf;
-    q.set_stride = p.set_stride;
-    q.rows_at = p.rows_at;
-    return q;
-}
-inline int fgram_blocks(const ForcesGramPlan& p) { return 8 * p.ntiles * ((p.nsets + 7) / 8); }
-
 // P2 of the forces kernels (k_strip, k_strip2): what a strip's column sums become before the row-sum product takes them
 enum StripMode : int {
     SM_BT = 0,          // pass 2 of the evaluation: b, t

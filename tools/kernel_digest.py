@@ -3,11 +3,14 @@
 
     tools/kernel_digest.py bioen_amd/csrc/kernels_forces.hip ... [--extra=-DSTRIP_DIAG=4] [-j 8] > table.txt
     tools/kernel_digest.py --compare before.txt after.txt
+    tools/kernel_digest.py old/kernels_x.hip --rename 11FGram16ArgsE=9FGramArgsE > before.txt
 
 Each file is compiled with the Makefile's flags plus `--cuda-device-only -S` into a temporary directory (no GPU needed).  A
 kernel's text runs from its label to its `.Lfunc_end`, the `.amdhsa_kernel` block included; before hashing, local labels are
 renumbered (`.LBB<n>_` -> `.LBB_`), comments dropped and whitespace collapsed, so that a kernel hashes the same whichever file
 it is compiled from and whatever stands in front of it there.  Two trees whose tables are equal run the same instructions.
+`--rename OLD=NEW` replaces OLD by NEW throughout the assembly before anything is hashed: for a kernel whose mangled name
+changed between the two trees (an argument struct renamed) and whose instructions are to be compared all the same.
 """
 import argparse
 import concurrent.futures
@@ -57,13 +60,16 @@ def kernels_of(asm):
     return out
 
 
-def digest_file(path, hipcc, flags, tmp):
+def digest_file(path, hipcc, flags, tmp, renames=()):
     s = os.path.join(tmp, os.path.basename(path) + ".s")
     r = subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", "-o", s, path], stderr=subprocess.PIPE, text=True)
     if r.returncode:
         sys.exit(r.stderr)
     with open(s) as f:
-        return kernels_of(f.read())
+        asm = f.read()
+    for old, new in renames:
+        asm = asm.replace(old, new)
+    return kernels_of(asm)
 
 
 def compare(a, b):
@@ -85,14 +91,16 @@ def main():
     ap.add_argument("files", nargs="*")
     ap.add_argument("--extra", action="append", default=[], help="a further compiler flag (the Makefile's EXTRA=)")
     ap.add_argument("-j", type=int, default=1, help="files compiled side by side")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="replace OLD by NEW in the assembly before hashing")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"), help="compare two tables written by this tool")
     args = ap.parse_args()
     if args.compare:
         return compare(*args.compare)
     hipcc, flags = makefile_flags()
+    renames = [tuple(r.split("=", 1)) for r in args.rename]
     merged = {}
     with tempfile.TemporaryDirectory() as tmp, concurrent.futures.ThreadPoolExecutor(args.j) as pool:
-        for ks in pool.map(lambda p: digest_file(p, hipcc, flags + args.extra, tmp), args.files):
+        for ks in pool.map(lambda p: digest_file(p, hipcc, flags + args.extra, tmp, renames), args.files):
             dup = merged.keys() & ks.keys()
             if dup:
                 sys.exit("kernel defined twice: " + sorted(dup)[0])
