@@ -57,6 +57,22 @@ class NewtonResult(C.Structure):
                 ("switched", C.c_int)]
 
 
+class LogwNewtonConfig(C.Structure):
+    # bioen_logwn_config (include/bioen_hip_logw_newton.h)
+    _fields_ = [("gtol", C.c_double), ("armijo", C.c_double), ("floor_ulps", C.c_double), ("max_iterations", C.c_int),
+                ("max_halvings", C.c_int)]
+
+
+class LogwNewtonResult(C.Structure):
+    # bioen_logwn_result (include/bioen_hip_logw_newton.h)
+    _fields_ = [("fmin", C.c_double), ("gmax", C.c_double), ("wmax", C.c_double), ("status", C.c_int),
+                ("iterations", C.c_int), ("evaluations", C.c_int), ("factorisations", C.c_int)]
+
+
+# the dual Newton minimizer's constants (log_weights.dual_newton_bioen_log_posterior_base uses the same)
+LOGW_NEWTON_DEFAULTS = dict(gtol=1e-6, max_iterations=200, armijo=1e-4, floor_ulps=8.0, max_halvings=60)
+
+
 # the Newton minimizer's damping constants (forces.newton_bioen_log_posterior_base uses the same)
 NEWTON_DEFAULTS = dict(gtol=1e-6, max_iterations=200, hessian="gram", armijo=1e-4, rho_good=0.75, lambda_factor=4.0,
                        lambda_first=1e-10, lambda_max=1e10, lambda_zero=1e-12, floor_ulps=8.0)
@@ -200,6 +216,13 @@ _SIGNATURES_FORCES_LAPLACE = {
     "bioen_laplace_forces": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp, dp, dp, dp, ip, dp, dp]),
 }
 
+# every symbol include/bioen_hip_logw_newton.h declares (the eighth public header: the log-weights method's dual Newton
+# minimizer and the covariance it is built on; its entries are bioen_logwn_*); bound by lib() beside the other seven
+_SIGNATURES_LOGW_NEWTON = {
+    "bioen_logwn_cov": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp]),
+    "bioen_logwn_opt": (C.c_int, [ctx_p, dp, dp, C.c_double, C.POINTER(LogwNewtonConfig), dp, C.POINTER(LogwNewtonResult)]),
+}
+
 _lib = None
 
 
@@ -231,6 +254,10 @@ def exported_symbols_forces_laplace():
     return sorted(_SIGNATURES_FORCES_LAPLACE)
 
 
+def exported_symbols_logw_newton():
+    return sorted(_SIGNATURES_LOGW_NEWTON)
+
+
 def lib():
     """Load libbioen_hip.so (once).  Raises if it has not been built."""
     global _lib
@@ -242,7 +269,8 @@ def lib():
                 "There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP, _SIGNATURES_FORCES_GRAM, _SIGNATURES_FORCES_COLQUAD,
-                      _SIGNATURES_FORCES_GRAM_BF16, _SIGNATURES_FORCES_NEWTON, _SIGNATURES_FORCES_LAPLACE):
+                      _SIGNATURES_FORCES_GRAM_BF16, _SIGNATURES_FORCES_NEWTON, _SIGNATURES_FORCES_LAPLACE,
+                      _SIGNATURES_LOGW_NEWTON):
             for name, (res, args) in table.items():
                 fn = getattr(L, name)          # AttributeError here = header/library mismatch
                 fn.restype = res
@@ -315,6 +343,13 @@ def newton_source(value):
     if v not in NEWTON_SOURCES:
         raise RuntimeError("newton:hessian=" + v + " not recognized (valid values = 'gram', 'gram_bf16')")
     return NEWTON_SOURCES.index(v)
+
+
+def logw_newton_config(params):
+    """params (a dict; missing keys take LOGW_NEWTON_DEFAULTS) -> LogwNewtonConfig"""
+    p = dict(LOGW_NEWTON_DEFAULTS, **(params or {}))
+    return LogwNewtonConfig(float(p["gtol"]), float(p["armijo"]), float(p["floor_ulps"]), int(p["max_iterations"]),
+                            int(p["max_halvings"]))
 
 
 def newton_config(params):
@@ -538,11 +573,12 @@ class Context(object):
         plus "bfgs_hinv" and its N x N bytes while a BFGS session (bfgs_logw) is live, and "forces_gram", the device buffer
         of forces_gram, "forces_colquad", the one of forces_colquad, "forces_gram_bf16", the one of forces_gram_bf16, and
         "forces_newton", the factor L and the work buffers of forces_newton_factor / opt_newton_forces, and "forces_laplace",
-        the inverse factor and the covariances of forces_inverse / forces_laplace, each from its first call on"""
+        the inverse factor and the covariances of forces_inverse / forces_laplace, and "logw_gram", the device buffer of logw_cov /
+        opt_dual_newton_logw, each from its first call on"""
         f, b = C.c_int(0), C.c_longlong(0)
         check(lib().bioen_hip_ctx_footprint(self._h, C.byref(f), C.byref(b)))
         names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced", 16: "bfgs_hinv", 32: "forces_gram",
-                 64: "forces_colquad", 128: "forces_gram_bf16", 256: "forces_newton", 512: "forces_laplace"}
+                 64: "forces_colquad", 128: "forces_gram_bf16", 256: "forces_newton", 512: "forces_laplace", 1024: "logw_gram"}
         return {names[k] for k in names if f.value & k}, b.value
 
     def layout(self):
@@ -655,6 +691,46 @@ class Context(object):
         grad = np.empty(self.n)
         check(lib().bioen_hip_logw_hessp(self._h, ptr(g), ptr(G), float(theta), k, ptr(va), ptr(hv), C.byref(f), ptr(grad)))
         return hv, f.value, grad
+
+    def logw_cov(self, g=None, G=None, theta=None, cov=True):
+        """C = sum_j w_j (y_j - ybar)(y_j - ybar)^T, w = softmax(g): the covariance of the observables (of the affine model if
+        one is set) under the weights of a log-weights point, (m, m), bitwise symmetric, the same bits call after call --
+        one compute-bound pass on the FP64 matrix cores (M <= 1024).  With `g` (and G, theta) the point is
+        evaluated first, as by logw_hessp -- f and grad are its bits --, and kept on the context: -> (C, f, grad); cov=False
+        then only sets the point (C is None).  Without, at the kept log-weights point (this call's, logw_hessp's or
+        opt_dual_newton_logw's): -> C; BioenHipError (invalid state) as logw_hessp raises it.  The first computing call
+        allocates a device buffer that stays with the context (footprint(): "logw_gram")."""
+        m = self.m
+        C_ = np.empty((m, m)) if cov else None
+        pc = ptr(C_) if cov else None
+        if g is None:
+            if not cov:
+                raise ValueError("logw_cov without g needs cov")
+            check(lib().bioen_logwn_cov(self._h, None, None, 0.0, pc, None, None))
+            return C_
+        if G is None or theta is None:
+            raise ValueError("logw_cov with g needs G and theta")
+        g, G = self._nvec(g, "g"), self._nvec(G, "G")
+        f = C.c_double(0.0)
+        grad = np.empty(self.n)
+        check(lib().bioen_logwn_cov(self._h, ptr(g), ptr(G), float(theta), pc, C.byref(f), ptr(grad)))
+        return C_, f.value, grad
+
+    def opt_dual_newton_logw(self, g0, G, theta, params=None):
+        """The dual Newton minimizer of the log-weights objective, the loop on the device side of the C ABI:
+        per iteration the covariance C of the kept point, (C + theta I) z = -b factorised and solved in HBM, one centred
+        adjoint pass, one evaluation per trial alpha = 1, 1/2, ...; params: gtol, max_iterations and the constants of
+        LOGW_NEWTON_DEFAULTS.  theta > 0.  -> dict(g, status (0: max|grad| <= gtol max w, 1: max_iterations, 2: step
+        exhausted at the rounding floor of f, 3: step exhausted), fmin, gmax, wmax, iterations, evaluations,
+        factorisations).  g is in the gauge the steps leave it in: compare weights.  The returned point is the context's
+        kept point: logw_cov() and logw_hessp(v) right after serve it."""
+        g0, G = self._nvec(g0, "g0"), self._nvec(G, "G")
+        cfg = logw_newton_config(params)
+        out = np.empty(self.n)
+        res = LogwNewtonResult()
+        check(lib().bioen_logwn_opt(self._h, ptr(g0), ptr(G), float(theta), C.byref(cfg), ptr(out), C.byref(res)))
+        return dict(g=out, status=res.status, fmin=res.fmin, gmax=res.gmax, wmax=res.wmax, iterations=res.iterations,
+                    evaluations=res.evaluations, factorisations=res.factorisations)
 
     def opt_lbfgs_logw(self, g0, G, theta, params, verbose=False, debug=False, want_weights=True):
         g0, G = self._nvec(g0, "g0"), self._nvec(G, "G")

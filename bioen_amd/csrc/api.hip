@@ -1258,7 +1258,7 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
         f |= 16;
         b += c->bfgs_hbytes;
     }
-    for (int i = 0; i < SCRATCH_COUNT; ++i)      // the dense forces entries' buffers (ctx.hpp: CtxScratch): 32, 64, 128, 256, 512
+    for (int i = 0; i < SCRATCH_COUNT; ++i)      // the dense forces entries' buffers (ctx.hpp: CtxScratch): 32, 64, 128, 256, 512, 1024
         if (c->scratch[i].p) {
             f |= 32 << i;
             b += c->scratch[i].bytes;
@@ -2214,3 +2214,4 @@ static void comm_release(bioen_hip_ctx* c) {
 #include "api_forces_colquad.inl"
 #include "api_forces_newton.inl"
 #include "api_forces_laplace.inl"
+#include "api_logw_newton.inl"

@@ -1,0 +1,214 @@
+// The log-weights method's dual Newton minimizer and the covariance it is built on (part of api.hip's translation unit: uses
+// its static helpers; kernels: kernels_logw_newton.hip).  N unknowns through an M x M system: C of the kept
+// log-weights point from k_logw_gram, C + theta I factorised and solved by section 6h's kernels (api_forces_newton.inl:
+// fnewton_factor, launch_fnewton_solve), the step from ONE centred adjoint pass on r + z.  Every N-vector stays in HBM; the
+// loop is log_weights.py's dual_newton_bioen_log_posterior_base, decision for decision.  The point is bioen_hip_logw_hessp's
+// (api_hessp.inl), the refusal without one api_forces_point.inl's need_point.
+
+#include "../../include/bioen_hip_logw_newton.h"
+
+namespace bioen {
+
+static const PointWords kLogwnPoint = {"call with g", "set a log-weights point first (bioen_logwn_cov or bioen_hip_logw_hessp with g)"};
+
+// What these entries refuse, each with a message of its own, before the device is touched
+static int logwn_guard(const bioen_hip_ctx* c, const char* who) {
+    const std::string w(who);
+    if (c->world != 1)
+        return fail(BIOEN_HIP_ESTATE, (w + " is not served on a structure-sharded context (the all-gather of the segments' "
+                                           "partial matrices is not built): use the L-BFGS there").c_str());
+    if (c->m > 1024)
+        return fail(BIOEN_HIP_ESTATE, (w + " serves M <= 1024 only (beyond, the matrix is held as row panels and there is no "
+                                           "Gram pass over them): use the L-BFGS there").c_str());
+    if (c->storage)
+        return fail(BIOEN_HIP_ESTATE, (w + " is not served on the reduced-storage experiment's copies "
+                                           "(bioen_hip_ctx_set_storage(0))").c_str());
+    if (fwd_strip_blocks(c) <= 0)
+        return fail(BIOEN_HIP_ESTATE, (w + " needs the strip copies of the matrix: the streaming kernels have no Gram product").c_str());
+    return 0;
+}
+
+// slot 0's x (and c->fixed = G) hold a point: bioen_hip_logw_hessp's evaluation of it, launch for launch, after which it is
+// the context's kept point; then the guard again -- the strip copies exist by now, or never will
+static int logwn_eval_point(bioen_hip_ctx* c, double theta, double* f, double* grad, const char* who) {
+    int rc;
+    c->point_lost = "a call that failed to set a new point";
+    if ((rc = hessp_buffers(c, 1))) return rc;
+    const int one[1] = {0};
+    if ((rc = eval_logw_point(c, make_round(c, one, 1, nullptr, &theta), true, true, f, grad))) return rc;
+    c->point_theta = theta;
+    c->point_kind = 0;
+    c->point_valid = 1;
+    c->point_lost = nullptr;
+    if ((rc = logwn_guard(c, who))) return rc;
+    return c->Ys[0] ? 0 : fail(BIOEN_HIP_ESTATE, (std::string(who) + " needs the strip copies of the matrix").c_str());
+}
+
+// C of the kept log-weights point into SCRATCH_LOGW_GRAM, not downloaded; negb (may be NULL): -Yc grad for the solve
+static int logwn_gram(bioen_hip_ctx* c, const double** cov, double* negb) {
+    int rc;
+    const LogwGramPlan p = logw_gram_plan(c);
+    if ((rc = ensure_scratch(c, SCRATCH_LOGW_GRAM, p.doubles))) return rc;
+    double* buf = c->scratch[SCRATCH_LOGW_GRAM].p;
+    const ProblemSlot& s0 = c->slot[0];
+    launch_logw_gram(c, p, buf, s0.w, s0.g, s0.scal, c->point_ybar, negb);
+    if ((rc = check_launch())) return rc;
+    if (cov) *cov = buf + p.cov_at;
+    return 0;
+}
+
+// max |grad|, max w, max |gamma| of the point slot 0 was just evaluated at
+static int logwn_stats(bioen_hip_ctx* c, double theta, double* gmax, double* wmax, double* gammamax) {
+    int rc;
+    const LogwGramPlan p = logw_gram_plan(c);
+    double* out = c->scratch[SCRATCH_LOGW_GRAM].p + p.vec_at;
+    const ProblemSlot& s0 = c->slot[0];
+    launch_logwn_stats(c, s0.x, s0.w, s0.g, s0.a, s0.scal, theta, out);
+    if ((rc = check_launch())) return rc;
+    double h[3];
+    BIOEN_HIP_CHECK(hipMemcpyAsync(h, out + LN_GMAX, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
+    *gmax = h[0], *wmax = h[1], *gammamax = h[2];
+    return 0;
+}
+
+}  // namespace bioen
+
+extern "C" int bioen_logwn_cov(bioen_hip_ctx* c, const double* g, const double* G, double theta, double* C, double* f,
+                               double* grad) {
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;      // a call rejected below leaves the point (and the device) alone
+    if (g && !G) return fail(BIOEN_HIP_EINVAL, "g without G");
+    if (!g && !C) return fail(BIOEN_HIP_EINVAL, "nothing to do: no g and no C");
+    int rc;
+    if ((rc = logwn_guard(c, __func__))) return rc;
+    if (!g && (rc = need_point(c, 0, __func__, &kLogwnPoint))) return rc;
+    if ((rc = enter(c, g ? FX_EVALUATES : FX_DEVICE, __func__))) return rc;
+    if (g) {
+        ProblemSlot& s0 = c->slot[0];
+        if ((rc = upload_n(c, s0.x, g))) return rc;
+        if ((rc = upload_n(c, c->fixed, G))) return rc;
+        BIOEN_HIP_CHECK(hipMemsetAsync(s0.d, 0, c->ld * sizeof(double), c->stream));
+        if ((rc = logwn_eval_point(c, theta, f, grad, __func__))) return rc;
+    }
+    if (!C) return 0;
+    const double* dcov = nullptr;
+    if ((rc = logwn_gram(c, &dcov, nullptr))) return rc;
+    BIOEN_HIP_CHECK(hipMemcpyAsync(C, dcov, (size_t)c->m * c->m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double* G, double theta,
+                               const bioen_logwn_config* cfg, double* gopt, bioen_logwn_result* res) {
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
+    if (!g0 || !G || !cfg || !gopt || !res) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (!(cfg->gtol >= 0.0) || cfg->max_iterations < 0 || cfg->max_halvings < 1 || !(cfg->armijo > 0.0) || !(cfg->floor_ulps >= 0.0))
+        return fail(BIOEN_HIP_EINVAL, "bioen_logwn_config: gtol >= 0, max_iterations >= 0, max_halvings >= 1, armijo > 0, floor_ulps >= 0");
+    int rc;
+    if (!(theta > 0.0) || !std::isfinite(theta))
+        return fail(BIOEN_HIP_EINVAL, "bioen_logwn_opt needs theta > 0 (the step divides by theta): use the L-BFGS for theta = 0");
+    if ((rc = logwn_guard(c, __func__))) return rc;
+    if ((rc = enter(c, FX_EVALUATES, __func__))) return rc;
+    const double eps = 2.220446049250313e-16;
+    ProblemSlot& s0 = c->slot[0];
+    *res = bioen_logwn_result{};
+    // slot 0: xp = the accepted point, d = the step u, x = the trial (k_trial: x = xp + alpha d), w, g, a, scal = the
+    // evaluation's; hp_vec[0] takes the adjoint of r + z
+    if ((rc = upload_n(c, s0.xp, g0))) return rc;
+    if ((rc = upload_n(c, c->fixed, G))) return rc;
+    BIOEN_HIP_CHECK(hipMemcpyAsync(s0.x, s0.xp, c->ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    BIOEN_HIP_CHECK(hipMemsetAsync(s0.d, 0, c->ld * sizeof(double), c->stream));
+    double f = 0.0, ft = 0.0, gmax = 0.0, wmax = 0.0, cmax = 0.0;
+    if ((rc = logwn_eval_point(c, theta, &f, nullptr, __func__))) return rc;
+    res->evaluations = 1;
+    if ((rc = fnewton_buffers(c))) return rc;
+    const LogwGramPlan plan = logw_gram_plan(c);
+    if ((rc = ensure_scratch(c, SCRATCH_LOGW_GRAM, plan.doubles))) return rc;
+    double* const scal = c->scratch[SCRATCH_LOGW_GRAM].p + plan.vec_at;
+    const FNewtonBuf nb = fnewton_layout(c);
+    if ((rc = logwn_stats(c, theta, &gmax, &wmax, &cmax))) return rc;
+    const int one[1] = {0};
+    int status = -1, at_x = 1;
+    for (;;) {
+        if (gmax <= cfg->gtol * wmax && cmax <= theta) {      // 1. the gradient test, and gamma's
+            status = 0;
+            break;
+        }
+        if (res->iterations >= cfg->max_iterations) {        // 2.
+            status = 1;
+            break;
+        }
+        // 3. C and -b of the kept point (= xp), (C + theta I) z = -b, the operand r + z, its adjoint, u and grad . u
+        const double* cov = nullptr;
+        if ((rc = logwn_gram(c, &cov, nb.X))) return rc;
+        int info = 0;
+        if ((rc = fnewton_factor(c, cov, theta, &info, nullptr))) return rc;
+        ++res->factorisations;
+        if (info != 0) {                                     // C is PSD and theta > 0: a pivot fails only on a point that is not finite
+            status = 3;
+            break;
+        }
+        launch_fnewton_solve(c, nb.L, nb.ldl, 1, nb.X, c->mp);
+        launch_logwn_operand(c, nb.X, c->hp_scal);
+        int nblk = 0;                                        // (the evaluation has built the copies the adjoint reads)
+        if ((rc = choose_logw_passes(c, true, 0, true, &nblk))) return rc;
+        if (nblk <= 0) return fail(BIOEN_HIP_ESTATE, "bioen_logwn_opt needs the strip copies of the matrix");
+        MVec8 out{}, sc{};
+        out.p[0] = c->hp_vec[0];
+        sc.p[0] = c->hp_scal;
+        c->last_width = 1;
+        c->last_pos = 0;
+        c->last_centered = false;
+        launch_adj_strip(c, 1, c->r_c, out, sc);
+        launch_logwn_step(c, s0.xp, c->hp_vec[0], s0.g, s0.scal, theta, s0.d, scal);
+        if ((rc = check_launch())) return rc;
+        double slope = 0.0;
+        BIOEN_HIP_CHECK(hipMemcpyAsync(&slope, scal + LN_SLOPE, sizeof slope, hipMemcpyDeviceToHost, c->stream));
+        BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
+        // 4. alpha = 1, 1/2, ...
+        double alpha = 1.0, gtmax = 0.0, wtmax = 0.0, ctmax = 0.0;
+        bool accepted = false;
+        for (int k = 0; k < cfg->max_halvings; ++k) {
+            Round r = make_round(c, one, 1, &alpha, &theta);
+            launch_trial(c, r);
+            point_drop(c, __func__);
+            if ((rc = logwn_eval_point(c, theta, &ft, nullptr, __func__))) return rc;
+            ++res->evaluations;
+            at_x = 0;
+            if ((rc = logwn_stats(c, theta, &gtmax, &wtmax, &ctmax))) return rc;
+            const bool floor = std::fabs(alpha * slope) <= cfg->floor_ulps * eps * std::fabs(f);
+            if (floor) {
+                if (std::isfinite(ft) && gtmax < gmax) accepted = true;
+                else status = 2;
+                break;
+            }
+            if (std::isfinite(ft) && ft - f <= cfg->armijo * alpha * slope) {
+                accepted = true;
+                break;
+            }
+            alpha *= 0.5;
+        }
+        if (!accepted) {
+            if (status < 0) status = 3;
+            break;
+        }
+        BIOEN_HIP_CHECK(hipMemcpyAsync(s0.xp, s0.x, c->ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        f = ft, gmax = gtmax, wmax = wtmax, cmax = ctmax;
+        at_x = 1;
+        ++res->iterations;
+    }
+    if (!at_x) {                                             // the returned point is the kept one
+        BIOEN_HIP_CHECK(hipMemcpyAsync(s0.x, s0.xp, c->ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        point_drop(c, __func__);
+        if ((rc = logwn_eval_point(c, theta, &f, nullptr, __func__))) return rc;
+        ++res->evaluations;
+        if ((rc = logwn_stats(c, theta, &gmax, &wmax, &cmax))) return rc;
+    }
+    if ((rc = download_n(c, gopt, s0.xp))) return rc;
+    BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
+    res->status = status;
+    res->fmin = f;
+    res->gmax = gmax;
+    res->wmax = wmax;
+    return 0;
+}

@@ -158,6 +158,8 @@ enum CtxScratch : int {
                          // (m x m), the right-hand sides (kMaxBatch x mp), the source's diagonal (mp) and the info word
     SCRATCH_LAPLACE,     // the Laplace error bars (api_forces_laplace.inl): W = L^-1, H^-1, B = W C and C H^-1 C (mp x mp each), then
                          // diag L, diag H^-1 and diag C H^-1 C (mp each)
+    SCRATCH_LOGW_GRAM,   // the log-weights dual Newton (api_logw_newton.inl): k_logw_gram's sets, their sum, C, and the loop's scalars
+                         // (kernels.hpp: LogwGramPlan)
     SCRATCH_COUNT
 };
 struct CtxScratchBuf {

@@ -203,6 +203,32 @@ void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, 
 // (k_fgram_sum_sets, k_fgram_finish, k_fgram_square, defined in kernels_forces_gram.hip)
 void launch_fgram_tail(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* ybar, double theta);
 
+void launch_fgram_sum_sets(bioen_hip_ctx* c, double* buf, size_t set_stride, int nlocal, int gs);   // the sets' sum alone, behind them
+
+// ---- the log-weights method's dual Newton step (kernels_logw_newton.hip): the covariance of the observables
+// under the weights of the kept log-weights point, ONE M x M x N product on the copy the forward pass reads, and the
+// vector kernels of the loop around it --------------------------------------------------------------------------------
+struct LogwGramPlan {
+    int nsl, ntiles, nsub;          // as ForcesGramPlan's
+    int gs, nsets;
+    size_t set_stride, rows_at;     // doubles per set; where a set's row sums of Y' grad begin (behind them: sum grad)
+    size_t cov_at, vec_at;          // behind the sets and their sum: C (m x m), then kLogwnScal scalars
+    size_t doubles;
+};
+enum LogwnScal : int { LN_GMAX = 0, LN_WMAX, LN_GAMMA, LN_SLOPE, kLogwnScal = 8 };
+LogwGramPlan logw_gram_plan(const bioen_hip_ctx* c);
+// the sets, their sum, C (affine model: S C S) at buf + cov_at; negb (may be NULL, mp doubles) <- -Yc grad (affine: S .)
+void launch_logw_gram(bioen_hip_ctx* c, const LogwGramPlan& p, double* buf, const double* e, const double* grad,
+                      const double* pscal, const double* ybar, double* negb);
+// operand <- r_c + row_scale o z (K = 1: the centred adjoint's operand), its constants S_B0, S_UY into scal
+void launch_logwn_operand(bioen_hip_ctx* c, const double* z, double* scal);
+// out[LN_GMAX, LN_WMAX, LN_GAMMA] <- max |grad|, max w, max |gamma|, gamma = theta (x - G - P) + a, of the evaluated slot
+void launch_logwn_stats(bioen_hip_ctx* c, const double* x, const double* e, const double* grad, const double* a,
+                        const double* pscal, double theta, double* out);
+// u = -[(x - G - P) + cadj / theta] (the padding zero); out[LN_SLOPE] <- grad . u
+void launch_logwn_step(bioen_hip_ctx* c, const double* x, const double* cadj, const double* grad, const double* pscal,
+                       double theta, double* u, double* out);
+
 // the same pass with split-BF16 operands on the BF16 matrix cores (kernels_forces_gram_bf16.hip): the plan, the
 // sets' layout and the tail are the FP64 pass's, buf is a buffer of its own
 void launch_forces_gram_bf16(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,

@@ -213,12 +213,18 @@ ForcesGramPlan forces_gram_plan(const bioen_hip_ctx* c) {
     return p;
 }
 
+// nlocal x gs sets of set_stride doubles in buf -> their sum in the fixed order, one more set behind them (the log-weights
+// Gram pass, kernels_logw_newton.hip, ends here too)
+void launch_fgram_sum_sets(bioen_hip_ctx* c, double* buf, size_t set_stride, int nlocal, int gs) {
+    const int sum_blocks = (int)std::min<size_t>((set_stride + kBlock - 1) / kBlock, 4096);
+    hipLaunchKernelGGL(k_fgram_sum_sets, dim3(sum_blocks), dim3(kBlock), 0, c->stream, buf, set_stride, set_stride, nlocal, gs,
+                       buf + (size_t)nlocal * gs * set_stride);
+}
+
 // the sets in buf -> their sum behind them, C at buf + cov_at, H at buf + hess_at (both passes end here)
 void launch_fgram_tail(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* ybar, double theta) {
     double* sum = buf + (size_t)p.nsets * p.set_stride;
-    const int sum_blocks = (int)std::min<size_t>((p.set_stride + kBlock - 1) / kBlock, 4096);
-    hipLaunchKernelGGL(k_fgram_sum_sets, dim3(sum_blocks), dim3(kBlock), 0, c->stream, buf, p.set_stride, p.set_stride, c->vr,
-                       p.gs, sum);
+    launch_fgram_sum_sets(c, buf, p.set_stride, c->vr, p.gs);
     const int tb = (c->m + 15) / 16;
     hipLaunchKernelGGL(k_fgram_finish, dim3(tb, tb), dim3(256), 0, c->stream, sum, p.rows_at, c->m, theta, ybar, c->row_scale,
                        c->affine, buf + p.cov_at, buf + p.hess_at);

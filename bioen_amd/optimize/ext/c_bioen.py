@@ -417,6 +417,24 @@ def bioen_opt_lbfgs_forces(forces, w0, yTilde, YTilde, theta, params):
     return res, info.fmin
 
 
+def bioen_opt_dual_newton_logw(g, G, yTilde, YTilde, theta, params):
+    """-> (gopt[n], fmin): the device-resident dual Newton minimizer of the log-weights method
+    (Context.opt_dual_newton_logw).  Status 0 returns; every other status raises RuntimeError with the return code, as
+    the other device minimizers do.  last_opt_info: the result dict."""
+    global last_opt_info
+    ctx, cached = _context_for(yTilde, YTilde)
+    try:
+        res = ctx.opt_dual_newton_logw(np.asarray(g, dtype=np.float64).reshape(-1),
+                                       np.asarray(G, dtype=np.float64).reshape(-1), theta, params["params"])
+    finally:
+        _release(ctx, cached)
+    last_opt_info = res
+    if res["status"] != 0:
+        raise RuntimeError("bioen_opt_dual_newton_logw: return code %d after %d iterations, max|grad| = %.3g, max w = %.3g"
+                           % (res["status"], res["iterations"], res["gmax"], res["wmax"]))
+    return res["g"], res["fmin"]
+
+
 def bioen_opt_newton_forces(forces, w0, yTilde, YTilde, theta, params):
     """-> (forces_opt[m], fmin): the device-resident Newton minimizer (Context.opt_newton_forces).  Status 0 (max|g| <=
     gtol) and 2 (at the minimum to the rounding of f) return; 1 (max_iterations) and 3 (the damping left its range) raise

@@ -167,6 +167,123 @@ def hessp_bioen_log_posterior_base(gPrime, p, g, G, yTilde, YTilde, theta):
     return hp[:, 0]
 
 
+# ------------------------------------------------------------------ the dual Newton minimizer
+#  N unknowns through an M x M system: with the gradient-proportional terms of the Hessian dropped,
+#   H~ = theta S + W Yc^T Yc W   (S = W - w w^T, Yc = yTilde - ybar 1^T; = H at the optimum),
+# the step H~ u = -grad, w . u = 0, is  (C + theta I) z = -Yc grad,  C = Yc W Yc^T,
+#   u = -[(dev - P) + (1 / theta) Yc^T (r + z)]      (dev = g - G, P = w . dev, r = ybar - YTilde)
+_DUAL_NEWTON_CONSTANTS = dict(armijo=1e-4, floor_ulps=8.0, max_halvings=60)
+DUAL_NEWTON_STATUS = {0: "max|grad| <= gtol max w", 1: "max_iterations reached",
+                      2: "step exhausted at the rounding floor of f", 3: "step exhausted"}
+
+
+def _dual_newton_point(g, G, yT, YT, theta, logs0):
+    """everything the loop keeps of a point: f, grad = w gamma, and the pieces of the step"""
+    shift = g.max()
+    e = np.exp(g - shift)
+    s = e.sum()
+    w = e / s
+    ybar = yT.dot(w)
+    r = ybar - YT
+    dev = g - G
+    P = float(w.dot(dev))
+    f = float(theta * (P - (np.log(s) + shift) + logs0) + 0.5 * r.dot(r))
+    gamma = theta * (dev - P) + (yT.T.dot(r) - float(ybar.dot(r)))
+    return dict(g=g, f=f, w=w, ybar=ybar, r=r, dev=dev, P=P, gamma=gamma, grad=w * gamma)
+
+
+def dual_newton_covariance(p, yT):
+    """C = Yc W Yc^T of a point of _dual_newton_point: the covariance of the observables under its weights"""
+    Yc = yT - p["ybar"][:, None]
+    return (Yc * p["w"]).dot(Yc.T)
+
+
+def dual_newton_step(p, yT, theta):
+    """(u, z) at a point of _dual_newton_point: one covariance, one Cholesky factorisation of C + theta I (SPD for
+    every theta > 0), one centred forward pass on grad, one centred adjoint pass on r + z"""
+    import scipy.linalg
+    Yc = yT - p["ybar"][:, None]
+    C = (Yc * p["w"]).dot(Yc.T)
+    b = Yc.dot(p["grad"])
+    L = np.linalg.cholesky(C + theta * np.eye(C.shape[0]))
+    z = -scipy.linalg.cho_solve((L, True), b)
+    u = -((p["dev"] - p["P"]) + Yc.T.dot(p["r"] + z) / theta)
+    return u, z
+
+
+def dual_newton_bioen_log_posterior_base(gInit, G, yTilde, YTilde, theta, params):
+    """The numpy statement of the dual Newton minimizer of the log-weights objective.
+
+      1. stop: max|grad| <= gtol max w (the weight gate is relative to max w, so the test is) AND max|gamma| <= theta,
+         grad = w gamma -> status 0.  The second half is the globalisation: where a step of size ~ 1 / theta has
+         collapsed the softmax onto a few structures, every w_k gamma_k is tiny although gamma is not; gamma_k / theta is
+         the change of log-weight k the mirror step still asks for, and at a minimum it is far below 1 for EVERY k (the
+         step sets the negligible structures' log-weights to exactly that).  A point that fails it is iterated on.
+      2. max_iterations accepted steps -> status 1.
+      3. u from dual_newton_step (one factorisation), slope = grad . u.
+      4. alpha = 1, 1/2, ...: f+ at g + alpha u; accept if f+ is finite and f+ - f <= 1e-4 alpha slope; at the rounding
+         floor (|alpha slope| <= 8 eps |f|: f cannot judge the step) accept on max|grad+| < max|grad| instead, and a
+         rejection there ends the run: status 2.  max_halvings rejections elsewhere: status 3.
+
+    -> dict(g, fmin, status, iterations, evaluations, factorisations, gmax, wmax).  theta <= 0 is refused: the step
+    divides by theta."""
+    theta = float(theta)
+    if not theta > 0.0:
+        raise RuntimeError("dual_newton needs theta > 0 (the step divides by theta), got %r" % theta)
+    c_ = dict(_DUAL_NEWTON_CONSTANTS, **{k: v for k, v in dict(params).items() if k in _DUAL_NEWTON_CONSTANTS})
+    gtol, maxit = float(params.get("gtol", 1e-6)), int(params.get("max_iterations", 200))
+    yT = np.asarray(yTilde, dtype=np.float64)
+    YT = np.asarray(YTilde, dtype=np.float64).reshape(-1)
+    Gv = np.asarray(G, dtype=np.float64).reshape(-1)
+    logs0 = float(np.log(np.exp(Gv - Gv.max()).sum()) + Gv.max())
+    eps = np.finfo(np.float64).eps
+    p = _dual_newton_point(np.asarray(gInit, dtype=np.float64).reshape(-1).copy(), Gv, yT, YT, theta, logs0)
+    count = dict(iterations=0, evaluations=1, factorisations=0)
+    status = None
+    while status is None:
+        gmax, wmax = float(np.abs(p["grad"]).max()), float(p["w"].max())
+        if gmax <= gtol * wmax and float(np.abs(p["gamma"]).max()) <= theta:
+            status = 0
+            break
+        if count["iterations"] >= maxit:
+            status = 1
+            break
+        u, _ = dual_newton_step(p, yT, theta)
+        count["factorisations"] += 1
+        slope = float(p["grad"].dot(u))
+        alpha, trial = 1.0, None
+        for _ in range(int(c_["max_halvings"])):
+            q = _dual_newton_point(p["g"] + alpha * u, Gv, yT, YT, theta, logs0)
+            count["evaluations"] += 1
+            floor = abs(alpha * slope) <= c_["floor_ulps"] * eps * abs(p["f"])
+            if floor:
+                if np.isfinite(q["f"]) and float(np.abs(q["grad"]).max()) < gmax:
+                    trial = q
+                else:
+                    status = 2
+                break
+            if np.isfinite(q["f"]) and q["f"] - p["f"] <= c_["armijo"] * alpha * slope:
+                trial = q
+                break
+            alpha *= 0.5
+        if trial is None:
+            status = status or 3
+            break
+        p = trial
+        count["iterations"] += 1
+    return dict(count, g=p["g"], fmin=p["f"], status=status, gmax=float(np.abs(p["grad"]).max()),
+                wmax=float(p["w"].max()))
+
+
+def _dual_newton_finish(who, res):
+    """status 0 returns; every other status raises with the return code, as the forces Newton does"""
+    if res["status"] != 0:
+        raise RuntimeError("%s: return code %d (%s) after %d iterations, max|grad| = %.3g, max w = %.3g"
+                           % (who, res["status"], DUAL_NEWTON_STATUS.get(res["status"], "?"), res["iterations"],
+                              res["gmax"], res["wmax"]))
+    return res["g"], res["fmin"]
+
+
 # ------------------------------------------------------------------ optimizer
 class _DeviceFdf(object):
     """scipy asks for f(x) and f'(x) in separate calls at the same x; one fused device
@@ -282,7 +399,7 @@ def _run_scipy(cfg, f, fprime, x0, args, flavour, show_caching, hessp=None):
 
 
 def _uses_device(cfg):
-    return not (str(cfg["minimizer"]).upper() == 'SCIPY' and not bool(cfg["use_c_functions"]))
+    return not (str(cfg["minimizer"]).upper() in ('SCIPY', 'DUAL_NEWTON') and not bool(cfg["use_c_functions"]))
 
 
 def _bfgs_on_device(cfg):
@@ -319,9 +436,11 @@ def find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg):
     matrix (none inside a caller's ``with optimize.resident(yTilde):``), as the reference's one ``yTilde.T.copy()`` per
     call (c_bioen.pyx:463-473)."""
     check_params_logweights(GInit, G, y, yTilde, YTilde)
-    if str(cfg["minimizer"]).upper() not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY'):      # rejected before anything touches the device
+    if str(cfg["minimizer"]).upper() not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY', 'DUAL_NEWTON'):      # rejected before anything touches the device
         raise RuntimeError("Library " + cfg["minimizer"] +
-                           " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy' ) ")
+                           " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy', 'dual_newton' ) ")
+    if str(cfg["minimizer"]).upper() == 'DUAL_NEWTON' and not float(theta) > 0.0:
+        raise RuntimeError("dual_newton needs theta > 0 (the step divides by theta), got %r" % float(theta))
     _bfgs_on_device(cfg)                                 # refused combinations raise here, before the device is touched
     if _uses_device(cfg):
         with c_bioen.hold(yTilde, YTilde):
@@ -344,11 +463,11 @@ def _find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg):
     cfg["cache_ytilde_transposed"] = caching      # the reference writes this back, :440
 
     minimizer = cfg["minimizer"].upper()
-    if minimizer not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY'):
+    if minimizer not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY', 'DUAL_NEWTON'):
         raise RuntimeError("Library " + cfg["minimizer"] +
-                           " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy' ) ")
+                           " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy', 'dual_newton' ) ")
     use_c = bool(cfg["use_c_functions"])
-    use_device = not (minimizer == 'SCIPY' and not use_c)
+    use_device = _uses_device(cfg)
 
     g = GInit.copy()
     gPrime = np.asarray(g[:].T)[0]
@@ -367,6 +486,13 @@ def _find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg):
     elif minimizer == 'GSL':
         common.print_highlighted("LOGW -- Library GSL/C", cfg["verbose"])
         res = c_bioen.bioen_opt_bfgs_logw(gPrime, G, yTilde, YTilde, theta, cfg)
+    elif minimizer == 'DUAL_NEWTON' and use_c:
+        common.print_highlighted("LOGW -- Library dual Newton/HIP", cfg["verbose"])
+        res = c_bioen.bioen_opt_dual_newton_logw(gPrime, G, yTilde, YTilde, theta, cfg)
+    elif minimizer == 'DUAL_NEWTON':
+        common.print_highlighted("LOGW -- Library dual Newton/PY", cfg["verbose"])
+        res = _dual_newton_finish("dual_newton_bioen_log_posterior_base",
+                                  dual_newton_bioen_log_posterior_base(gPrime, G, yTilde, YTilde, theta, cfg["params"]))
     elif minimizer == 'SCIPY' and use_c and _bfgs_on_device(cfg):
         common.print_highlighted("LOGW -- Library scipy-BFGS/HIP, inverse Hessian in HBM", cfg["verbose"])
         res = _run_device_bfgs(cfg, gPrime, G, yTilde, YTilde, theta)
