@@ -11,7 +11,7 @@
 //   end     w, chi^2, S at x; H is freed
 //
 // A session lives on an UNSHARDED context only.  Which other calls on the context end it is each entry's declaration to
-// the guard (api.hip: enter); every error inside a bfgs call ends it too, and bioen_hip_ctx_destroy.
+// the guard (host.hpp: enter); every error inside a bfgs call ends it too, and bioen_hip_ctx_destroy.
 
 namespace bioen {
 

@@ -41,6 +41,16 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert not extra, "bound in _lib.py but not declared in the header: %s" % extra
 
 
+def test_only_the_abi_is_exported_under_c_names():
+    """every defined dynamic symbol that is neither C++-mangled (_Z...) nor the toolchain's (__...) is an entry of the
+    C ABI: a helper that leaks out under a plain C name can be interposed by any other object in the process"""
+    from bioen_amd import _lib
+    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
+    names = set(line.split()[-1] for line in out.splitlines() if line.strip())
+    stray = sorted(n for n in names if not n.startswith(("_Z", "__", "bioen_")))
+    assert not stray, "exported under C names without being part of the ABI: %s" % stray
+
+
 def test_struct_layouts_match_the_reference_packing():
     from bioen_amd import _lib
     # lbfgs_config_params of c_bioen_common.h:69-79: int,int,5 doubles,int,int -> 56 bytes on LP64
