@@ -666,30 +666,38 @@ class Context(object):
         the context: -> (hv, f, grad); `v` None then only sets the point: -> (None, f, grad).  Without `g` the product
         refers to the point the last such call left: -> hv; BioenHipError (invalid state) once any other evaluation,
         optimizer or change of the matrix state has run."""
+        return self._hessp(lib().bioen_hip_logw_hessp, "logw_hessp", "N", ("g", "G"), v, g, G, theta)
+
+    def _point(self, dim, names, x, aux):
+        """the two vectors of a point -- the first of length N or M (`dim`), the second of length N, `names` in the
+        ValueError texts -- and what its evaluation leaves: f and grad, of the first vector's length"""
+        x = (self._nvec if dim == "N" else self._mvec)(x, names[0])
+        return x, self._nvec(aux, names[1]), C.c_double(0.0), np.empty(x.shape[0])
+
+    def _hessp(self, fn, name, dim, names, v, x, aux, theta):
+        """logw_hessp and forces_hessp: one call shape.  `fn` the entry, `dim` ("N" or "M") the length of a direction and of
+        the point's first vector, `names` the point's two arguments and `name` the method in the ValueError texts"""
         if v is None:
-            if g is None or G is None or theta is None:
-                raise ValueError("logw_hessp without v sets the point: it needs g, G and theta")
-            g, G = self._nvec(g, "g"), self._nvec(G, "G")
-            f = C.c_double(0.0)
-            grad = np.empty(self.n)
-            check(lib().bioen_hip_logw_hessp(self._h, ptr(g), ptr(G), float(theta), 0, None, None, C.byref(f), ptr(grad)))
+            if x is None or aux is None or theta is None:
+                raise ValueError("%s without v sets the point: it needs %s, %s and theta" % ((name,) + names))
+            x, aux, f, grad = self._point(dim, names, x, aux)
+            check(fn(self._h, ptr(x), ptr(aux), float(theta), 0, None, None, C.byref(f), ptr(grad)))
             return None, f.value, grad
         va = as_f64(v)
-        if va.ndim not in (1, 2) or va.shape[-1] != self.n:
-            raise ValueError("v must be (N,) or (k, N) with N = %d, got %s" % (self.n, (va.shape,)))
+        size = self.n if dim == "N" else self.m
+        if va.ndim not in (1, 2) or va.shape[-1] != size:
+            raise ValueError("v must be (%s,) or (k, %s) with %s = %d, got %s" % (dim, dim, dim, size, (va.shape,)))
         k = 1 if va.ndim == 1 else va.shape[0]
         if k < 1 or k > 8:
-            raise ValueError("logw_hessp takes 1 to 8 directions per call, got %d" % k)
+            raise ValueError("%s takes 1 to 8 directions per call, got %d" % (name, k))
         hv = np.empty_like(va)
-        if g is None:
-            check(lib().bioen_hip_logw_hessp(self._h, None, None, 0.0, k, ptr(va), ptr(hv), None, None))
+        if x is None:
+            check(fn(self._h, None, None, 0.0, k, ptr(va), ptr(hv), None, None))
             return hv
-        if G is None or theta is None:
-            raise ValueError("logw_hessp with g needs G and theta")
-        g, G = self._nvec(g, "g"), self._nvec(G, "G")
-        f = C.c_double(0.0)
-        grad = np.empty(self.n)
-        check(lib().bioen_hip_logw_hessp(self._h, ptr(g), ptr(G), float(theta), k, ptr(va), ptr(hv), C.byref(f), ptr(grad)))
+        if aux is None or theta is None:
+            raise ValueError("%s with %s needs %s and theta" % ((name,) + names))
+        x, aux, f, grad = self._point(dim, names, x, aux)
+        check(fn(self._h, ptr(x), ptr(aux), float(theta), k, ptr(va), ptr(hv), C.byref(f), ptr(grad)))
         return hv, f.value, grad
 
     def logw_cov(self, g=None, G=None, theta=None, cov=True):
@@ -700,21 +708,8 @@ class Context(object):
         then only sets the point (C is None).  Without, at the kept log-weights point (this call's, logw_hessp's or
         opt_dual_newton_logw's): -> C; BioenHipError (invalid state) as logw_hessp raises it.  The first computing call
         allocates a device buffer that stays with the context (footprint(): "logw_gram")."""
-        m = self.m
-        C_ = np.empty((m, m)) if cov else None
-        pc = ptr(C_) if cov else None
-        if g is None:
-            if not cov:
-                raise ValueError("logw_cov without g needs cov")
-            check(lib().bioen_logwn_cov(self._h, None, None, 0.0, pc, None, None))
-            return C_
-        if G is None or theta is None:
-            raise ValueError("logw_cov with g needs G and theta")
-        g, G = self._nvec(g, "g"), self._nvec(G, "G")
-        f = C.c_double(0.0)
-        grad = np.empty(self.n)
-        check(lib().bioen_logwn_cov(self._h, ptr(g), ptr(G), float(theta), pc, C.byref(f), ptr(grad)))
-        return C_, f.value, grad
+        out = self._gram(lib().bioen_logwn_cov, "logw_cov", "N", ("g", "G"), g, G, theta, cov=cov)
+        return out[0] if g is None else out
 
     def opt_dual_newton_logw(self, g0, G, theta, params=None):
         """The dual Newton minimizer of the log-weights objective, the loop on the device side of the C ABI:
@@ -881,32 +876,7 @@ class Context(object):
         None then only sets the point: -> (None, f, grad).  Without `forces` the product refers to the point the last such
         call left (two fused matrix passes, whatever k): -> hv; BioenHipError (invalid state) once any other evaluation,
         optimizer or change of the matrix state has run, or when the context's point is a log-weights point."""
-        fn = lib().bioen_hip_forces_hessp
-        if v is None:
-            if forces is None or w0 is None or theta is None:
-                raise ValueError("forces_hessp without v sets the point: it needs forces, w0 and theta")
-            fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
-            f = C.c_double(0.0)
-            grad = np.empty(self.m)
-            check(fn(self._h, ptr(fo), ptr(w0), float(theta), 0, None, None, C.byref(f), ptr(grad)))
-            return None, f.value, grad
-        va = as_f64(v)
-        if va.ndim not in (1, 2) or va.shape[-1] != self.m:
-            raise ValueError("v must be (M,) or (k, M) with M = %d, got %s" % (self.m, (va.shape,)))
-        k = 1 if va.ndim == 1 else va.shape[0]
-        if k < 1 or k > 8:
-            raise ValueError("forces_hessp takes 1 to 8 directions per call, got %d" % k)
-        hv = np.empty_like(va)
-        if forces is None:
-            check(fn(self._h, None, None, 0.0, k, ptr(va), ptr(hv), None, None))
-            return hv
-        if w0 is None or theta is None:
-            raise ValueError("forces_hessp with forces needs w0 and theta")
-        fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
-        f = C.c_double(0.0)
-        grad = np.empty(self.m)
-        check(fn(self._h, ptr(fo), ptr(w0), float(theta), k, ptr(va), ptr(hv), C.byref(f), ptr(grad)))
-        return hv, f.value, grad
+        return self._hessp(lib().bioen_hip_forces_hessp, "forces_hessp", "M", ("forces", "w0"), v, forces, w0, theta)
 
     def forces_hessian(self, forces=None, w0=None, theta=None):
         """The dense Hessian (m, m) of the forces objective: ceil(m / 8) forces_hessp calls with unit directions.  With
@@ -940,7 +910,7 @@ class Context(object):
         The first call allocates a device buffer for the partial sums that stays with the context (footprint():
         "forces_gram"): O(sets x m^2) whatever n is -- 117 MB at m = 256, 139 MB at m = 512, 168 MB at m = 1024 -- so with
         many small contexts prefer forces_hessian."""
-        return self._forces_gram(lib().bioen_hip_forces_gram, "forces_gram", forces, w0, theta, cov, hess)
+        return self._gram(lib().bioen_hip_forces_gram, "forces_gram", "M", ("forces", "w0"), forces, w0, theta, cov=cov, hess=hess)
 
     def forces_gram_bf16(self, forces=None, w0=None, theta=None, cov=True, hess=True):
         """(C~, H~): forces_gram's C and H with the two M x M x N products formed from split-BF16 operands (every operand
@@ -952,26 +922,25 @@ class Context(object):
         the point is kept; without -> (C~, H~) at the kept point.  Both matrices are bitwise symmetric and the same bits
         call after call.  The first computing call allocates a device buffer of forces_gram's size that stays with the
         context (footprint(): "forces_gram_bf16")."""
-        return self._forces_gram(lib().bioen_hip_forces_gram_bf16, "forces_gram_bf16", forces, w0, theta, cov, hess)
+        return self._gram(lib().bioen_hip_forces_gram_bf16, "forces_gram_bf16", "M", ("forces", "w0"), forces, w0, theta, cov=cov,
+                          hess=hess)
 
-    def _forces_gram(self, fn, name, forces, w0, theta, cov, hess):
-        """forces_gram and forces_gram_bf16: one call shape, `fn` the entry and `name` the method in the ValueError texts"""
-        m = self.m
-        C_ = np.empty((m, m)) if cov else None
-        H = np.empty((m, m)) if hess else None
-        pc, ph = (ptr(C_) if cov else None), (ptr(H) if hess else None)
-        if forces is None:
-            if not (cov or hess):
-                raise ValueError("%s without forces needs cov or hess" % name)
-            check(fn(self._h, None, None, 0.0, pc, ph, None, None))
-            return C_, H
-        if w0 is None or theta is None:
-            raise ValueError("%s with forces needs w0 and theta" % name)
-        fo, w0 = self._mvec(forces, "forces"), self._nvec(w0, "w0")
-        f = C.c_double(0.0)
-        grad = np.empty(m)
-        check(fn(self._h, ptr(fo), ptr(w0), float(theta), pc, ph, C.byref(f), ptr(grad)))
-        return C_, H, f.value, grad
+    def _gram(self, fn, name, dim, names, x, aux, theta, **want):
+        """forces_gram, forces_gram_bf16 and logw_cov: one call shape.  `fn` the entry, `name` the method in the ValueError
+        texts, `dim` and `names` the point's as in _hessp, `want` which of the entry's (m, m) matrices are asked for, by
+        the method's flags in the entry's order.  -> the matrices (None where not wanted), with a point then f and grad"""
+        mats = [np.empty((self.m, self.m)) if on else None for on in want.values()]
+        ptrs = [ptr(a) if a is not None else None for a in mats]
+        if x is None:
+            if not any(want.values()):
+                raise ValueError("%s without %s needs %s" % (name, names[0], " or ".join(want)))
+            check(fn(self._h, None, None, 0.0, *ptrs, None, None))
+            return tuple(mats)
+        if aux is None or theta is None:
+            raise ValueError("%s with %s needs %s and theta" % ((name,) + names))
+        x, aux, f, grad = self._point(dim, names, x, aux)
+        check(fn(self._h, ptr(x), ptr(aux), float(theta), *ptrs, C.byref(f), ptr(grad)))
+        return (*mats, f.value, grad)
 
     def forces_newton_factor(self, A=None, source="gram", lam=0.0, want_L=True):
         """(L or None, info): the FP64 Cholesky factorisation A + lam I = L L^T on the device (M <= 1024).  A: an

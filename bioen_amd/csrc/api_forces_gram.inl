@@ -15,7 +15,7 @@ static int fgram_compute(bioen_hip_ctx* c, int source, const double** cov, const
     if (!source) c->fgram_fresh = 0;
     if (forces_fused_blocks(c) <= 0) return fail(BIOEN_HIP_ESTATE, "the strip passes no longer serve this context");
     if ((rc = ensure_strip_copy(c, 1))) return rc;
-    const ForcesGramPlan p = forces_gram_plan(c);
+    const GramPlan p = forces_gram_plan(c);
     const int which = source ? SCRATCH_GRAM16 : SCRATCH_GRAM;
     if ((rc = ensure_scratch(c, which, p.doubles))) return rc;
     double* buf = c->scratch[which].p;
@@ -24,7 +24,7 @@ static int fgram_compute(bioen_hip_ctx* c, int source, const double** cov, const
     if ((rc = check_launch())) return rc;
     if (!source) c->fgram_fresh = 1;                          // (bioen_laplace_forces at the same kept point takes them as they stand)
     if (cov) *cov = buf + p.cov_at;
-    if (hess) *hess = buf + p.hess_at;
+    if (hess) *hess = buf + p.tail_at;
     return 0;
 }
 

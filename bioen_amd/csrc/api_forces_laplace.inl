@@ -55,9 +55,9 @@ static int flaplace_inverse(bioen_hip_ctx* c, const double* src, int* info, std:
 // changed since (ctx.hpp: fgram_fresh -- the same bits a new pass would write), else computed now
 static int flaplace_gram(bioen_hip_ctx* c, const double** cov, const double** hess) {
     if (!c->fgram_fresh || !c->scratch[SCRATCH_GRAM].p) return fgram_compute(c, 0, cov, hess);
-    const ForcesGramPlan p = forces_gram_plan(c);
+    const GramPlan p = forces_gram_plan(c);
     *cov = c->scratch[SCRATCH_GRAM].p + p.cov_at;
-    *hess = c->scratch[SCRATCH_GRAM].p + p.hess_at;
+    *hess = c->scratch[SCRATCH_GRAM].p + p.tail_at;
     return 0;
 }
 

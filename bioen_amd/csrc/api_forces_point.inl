@@ -1,12 +1,14 @@
 // What the entries that work at a kept point share (part of api.hip's translation unit: uses its static helpers; included in
-// front of api_hessp.inl and the api_forces_*.inl files): the refusal without a point of the right kind, the prologue of
-// the forces entries that set a point or serve the kept one, the guard of the dense entries (M <= 1024, one GPU, the FP64
-// strip copies) and the scratch buffers the context keeps for them.  DESIGN section 6c has the rules.
+// front of api_hessp.inl, the api_forces_*.inl files and api_logw_newton.inl): the refusal without a point of the right
+// kind, the prologues of the entries that set a point or serve the kept one -- the forces entries' and the log-weights
+// entries' --, the guard of the dense entries (M <= 1024, one GPU, the FP64 strip copies) and the scratch buffers the
+// context keeps for them.  DESIGN section 6c has the rules.
 
 namespace bioen {
 
 static int fhp_set_point(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* f, double* grad,
                          const char* who);      // api_forces_hessp.inl
+static int hessp_buffers(bioen_hip_ctx* c, int k);      // api_hessp.inl
 
 // Where an entry's refusal without a point reads differently from the kind's own, it stands behind "<who>: " with these
 // words: last, the call whose point is gone; remedy, what to do about it
@@ -42,6 +44,34 @@ static int forces_point_prologue(bioen_hip_ctx* c, const double* forces, const d
     return enter(c, FX_DEVICE, who);
 }
 
+// Slot 0's x (and c->fixed = G) hold a log-weights point: bioen_hip_logw_fdf's evaluation of it, launch for launch, after
+// which it is the context's kept point.  k: the directions hessp_buffers provides for
+static int logw_keep_point(bioen_hip_ctx* c, double theta, int k, double* f, double* grad) {
+    int rc;
+    c->point_lost = "a call that failed to set a new point";
+    if ((rc = hessp_buffers(c, k))) return rc;
+    const int one[1] = {0};
+    if ((rc = eval_logw_point(c, make_round(c, one, 1, nullptr, &theta), true, true, f, grad))) return rc;
+    c->point_theta = theta;
+    c->point_kind = 0;
+    c->point_valid = 1;
+    c->point_lost = nullptr;
+    return 0;
+}
+
+// The point of a log-weights entry `who`, as forces_point_prologue: with g it is an evaluation at (g, G), declared under the
+// entry's name, that leaves a new point; without, the kept log-weights point serves
+static int logw_point_prologue(bioen_hip_ctx* c, const double* g, const double* G, double theta, int k, double* f,
+                               double* grad, const char* who, const PointWords* words = nullptr) {
+    int rc;
+    if (!g) return (rc = need_point(c, 0, who, words)) ? rc : enter(c, FX_DEVICE, who);
+    if ((rc = enter(c, FX_EVALUATES, who))) return rc;
+    ProblemSlot& s0 = c->slot[0];
+    if ((rc = upload_n(c, s0.x, g)) || (rc = upload_n(c, c->fixed, G))) return rc;
+    BIOEN_HIP_CHECK(hipMemsetAsync(s0.d, 0, c->ld * sizeof(double), c->stream));
+    return logw_keep_point(c, theta, k, f, grad);
+}
+
 // What the dense entries refuse, each with a message of its own: the frame is shared, an entry's reasons fill it
 struct DenseReasons {
     const char *sharded, *panels, *product;
@@ -55,8 +85,14 @@ static const DenseReasons kColquadReasons = {
 static const DenseReasons kNewtonReasons = {
     "the Hessian pass is not built there): use the L-BFGS, or bioen_hip_forces_hessp with a host driver",
     " and there is no dense Hessian pass): use the L-BFGS there", "Gram product"};
+static const DenseReasons kLogwnReasons = {
+    "the all-gather of the segments' partial matrices is not built): use the L-BFGS there",
+    " and there is no Gram pass over them): use the L-BFGS there", "Gram product"};
 
-static int dense_guard(const bioen_hip_ctx* c, const char* who, const DenseReasons& why) {
+// strip_blocks: the strip passes whose copy the entry reads -- the forces method's, or fwd_strip_blocks for the log-weights
+// entries
+static int dense_guard(const bioen_hip_ctx* c, const char* who, const DenseReasons& why,
+                       int (*strip_blocks)(const bioen_hip_ctx*) = forces_fused_blocks) {
     const std::string w(who);
     if (c->world != 1)
         return fail(BIOEN_HIP_ESTATE, (w + " is not served on a structure-sharded context (" + why.sharded).c_str());
@@ -65,7 +101,7 @@ static int dense_guard(const bioen_hip_ctx* c, const char* who, const DenseReaso
     if (c->storage)
         return fail(BIOEN_HIP_ESTATE, (w + " is not served on the reduced-storage experiment's copies "
                                            "(bioen_hip_ctx_set_storage(0))").c_str());
-    if (forces_fused_blocks(c) <= 0)
+    if (strip_blocks(c) <= 0)
         return fail(BIOEN_HIP_ESTATE, (w + " needs the strip copies of the matrix: the streaming kernels have no " +
                                        why.product).c_str());
     return 0;

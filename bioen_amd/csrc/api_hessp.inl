@@ -5,7 +5,8 @@
 // the gradient and the scalars, c->fixed the prior G, point_ybar the raw averages, point_fac every segment's softmax
 // factor.  A product at the kept point is then what a gradient costs: three N-vector sweeps around one forward and one
 // centred adjoint pass -- the context's own pass family, for up to kMaxBatch directions at once.
-// The refusal without a point is api_forces_point.inl's need_point, the forces entries' too.
+// Whether a call sets the point or serves the kept one, and the refusal without one, is api_forces_point.inl's
+// logw_point_prologue, the dual Newton entries' too (api_logw_newton.inl).
 
 namespace bioen {
 
@@ -97,23 +98,8 @@ extern "C" int bioen_hip_logw_hessp(bioen_hip_ctx* c, const double* g, const dou
     if (k > 0 && (!v || !hv)) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (g && !G) return fail(BIOEN_HIP_EINVAL, "g without G");
     int rc;
-    if (!g && (rc = need_point(c, 0, __func__))) return rc;      // ONE point per context, of either method (api_forces_point.inl)
-    if ((rc = enter(c, g ? FX_EVALUATES : FX_DEVICE, __func__))) return rc;      // ... with g it is an evaluation
-    if (g) {
-        c->point_lost = "a call that failed to set a new point";
-        if ((rc = hessp_buffers(c, 0))) return rc;
-        ProblemSlot& s0 = c->slot[0];
-        if ((rc = upload_n(c, s0.x, g))) return rc;
-        if ((rc = upload_n(c, c->fixed, G))) return rc;
-        BIOEN_HIP_CHECK(hipMemsetAsync(s0.d, 0, c->ld * sizeof(double), c->stream));
-        const int one[1] = {0};
-        // bioen_hip_logw_fdf's evaluation, launch for launch
-        if ((rc = eval_logw_point(c, make_round(c, one, 1, nullptr, &theta), true, true, f, grad))) return rc;
-        c->point_theta = theta;
-        c->point_kind = 0;
-        c->point_valid = 1;
-        c->point_lost = nullptr;
-    }
+    // ONE point per context, of either method (api_forces_point.inl) ... with g it is an evaluation
+    if ((rc = logw_point_prologue(c, g, G, theta, 0, f, grad, __func__))) return rc;
     if (k == 0) return 0;
     rc = hessp_products(c, k, v, hv);
     if (rc) point_drop(c, "a product on it that failed");

@@ -2,8 +2,8 @@
 // its static helpers; kernels: kernels_logw_newton.hip).  N unknowns through an M x M system: C of the kept
 // log-weights point from k_logw_gram, C + theta I factorised and solved by section 6h's kernels (api_forces_newton.inl:
 // fnewton_factor, launch_fnewton_solve), the step from ONE centred adjoint pass on r + z.  Every N-vector stays in HBM; the
-// loop is log_weights.py's dual_newton_bioen_log_posterior_base, decision for decision.  The point is bioen_hip_logw_hessp's
-// (api_hessp.inl), the refusal without one api_forces_point.inl's need_point.
+// loop is log_weights.py's dual_newton_bioen_log_posterior_base, decision for decision.  The point is bioen_hip_logw_hessp's:
+// set, kept and refused by api_forces_point.inl's logw_point_prologue / logw_keep_point, the entries guarded by its dense_guard.
 
 #include "../../include/bioen_hip_logw_newton.h"
 
@@ -11,43 +11,23 @@ namespace bioen {
 
 static const PointWords kLogwnPoint = {"call with g", "set a log-weights point first (bioen_logwn_cov or bioen_hip_logw_hessp with g)"};
 
-// What these entries refuse, each with a message of its own, before the device is touched
-static int logwn_guard(const bioen_hip_ctx* c, const char* who) {
-    const std::string w(who);
-    if (c->world != 1)
-        return fail(BIOEN_HIP_ESTATE, (w + " is not served on a structure-sharded context (the all-gather of the segments' "
-                                           "partial matrices is not built): use the L-BFGS there").c_str());
-    if (c->m > 1024)
-        return fail(BIOEN_HIP_ESTATE, (w + " serves M <= 1024 only (beyond, the matrix is held as row panels and there is no "
-                                           "Gram pass over them): use the L-BFGS there").c_str());
-    if (c->storage)
-        return fail(BIOEN_HIP_ESTATE, (w + " is not served on the reduced-storage experiment's copies "
-                                           "(bioen_hip_ctx_set_storage(0))").c_str());
-    if (fwd_strip_blocks(c) <= 0)
-        return fail(BIOEN_HIP_ESTATE, (w + " needs the strip copies of the matrix: the streaming kernels have no Gram product").c_str());
-    return 0;
+// After a point's evaluation the guard once more (dense_guard, on the copy the log-weights forward pass reads): the strip
+// copies exist by now, or never will
+static int logwn_copies(const bioen_hip_ctx* c, const char* who) {
+    if (int rc = dense_guard(c, who, kLogwnReasons, fwd_strip_blocks)) return rc;
+    return c->Ys[0] ? 0 : fail(BIOEN_HIP_ESTATE, (std::string(who) + " needs the strip copies of the matrix").c_str());
 }
 
-// slot 0's x (and c->fixed = G) hold a point: bioen_hip_logw_hessp's evaluation of it, launch for launch, after which it is
-// the context's kept point; then the guard again -- the strip copies exist by now, or never will
-static int logwn_eval_point(bioen_hip_ctx* c, double theta, double* f, double* grad, const char* who) {
-    int rc;
-    c->point_lost = "a call that failed to set a new point";
-    if ((rc = hessp_buffers(c, 1))) return rc;
-    const int one[1] = {0};
-    if ((rc = eval_logw_point(c, make_round(c, one, 1, nullptr, &theta), true, true, f, grad))) return rc;
-    c->point_theta = theta;
-    c->point_kind = 0;
-    c->point_valid = 1;
-    c->point_lost = nullptr;
-    if ((rc = logwn_guard(c, who))) return rc;
-    return c->Ys[0] ? 0 : fail(BIOEN_HIP_ESTATE, (std::string(who) + " needs the strip copies of the matrix").c_str());
+// the loop's evaluations: what slot 0's x holds becomes the kept point (k = 1: hp_vec[0] takes the adjoint of r + z)
+static int logwn_keep_point(bioen_hip_ctx* c, double theta, double* f, const char* who) {
+    if (int rc = logw_keep_point(c, theta, 1, f, nullptr)) return rc;
+    return logwn_copies(c, who);
 }
 
 // C of the kept log-weights point into SCRATCH_LOGW_GRAM, not downloaded; negb (may be NULL): -Yc grad for the solve
 static int logwn_gram(bioen_hip_ctx* c, const double** cov, double* negb) {
     int rc;
-    const LogwGramPlan p = logw_gram_plan(c);
+    const GramPlan p = logw_gram_plan(c);
     if ((rc = ensure_scratch(c, SCRATCH_LOGW_GRAM, p.doubles))) return rc;
     double* buf = c->scratch[SCRATCH_LOGW_GRAM].p;
     const ProblemSlot& s0 = c->slot[0];
@@ -60,8 +40,8 @@ static int logwn_gram(bioen_hip_ctx* c, const double** cov, double* negb) {
 // max |grad|, max w, max |gamma| of the point slot 0 was just evaluated at
 static int logwn_stats(bioen_hip_ctx* c, double theta, double* gmax, double* wmax, double* gammamax) {
     int rc;
-    const LogwGramPlan p = logw_gram_plan(c);
-    double* out = c->scratch[SCRATCH_LOGW_GRAM].p + p.vec_at;
+    const GramPlan p = logw_gram_plan(c);
+    double* out = c->scratch[SCRATCH_LOGW_GRAM].p + p.tail_at;
     const ProblemSlot& s0 = c->slot[0];
     launch_logwn_stats(c, s0.x, s0.w, s0.g, s0.a, s0.scal, theta, out);
     if ((rc = check_launch())) return rc;
@@ -80,16 +60,9 @@ extern "C" int bioen_logwn_cov(bioen_hip_ctx* c, const double* g, const double* 
     if (g && !G) return fail(BIOEN_HIP_EINVAL, "g without G");
     if (!g && !C) return fail(BIOEN_HIP_EINVAL, "nothing to do: no g and no C");
     int rc;
-    if ((rc = logwn_guard(c, __func__))) return rc;
-    if (!g && (rc = need_point(c, 0, __func__, &kLogwnPoint))) return rc;
-    if ((rc = enter(c, g ? FX_EVALUATES : FX_DEVICE, __func__))) return rc;
-    if (g) {
-        ProblemSlot& s0 = c->slot[0];
-        if ((rc = upload_n(c, s0.x, g))) return rc;
-        if ((rc = upload_n(c, c->fixed, G))) return rc;
-        BIOEN_HIP_CHECK(hipMemsetAsync(s0.d, 0, c->ld * sizeof(double), c->stream));
-        if ((rc = logwn_eval_point(c, theta, f, grad, __func__))) return rc;
-    }
+    if ((rc = dense_guard(c, __func__, kLogwnReasons, fwd_strip_blocks))) return rc;
+    if ((rc = logw_point_prologue(c, g, G, theta, 1, f, grad, __func__, &kLogwnPoint))) return rc;
+    if (g && (rc = logwn_copies(c, __func__))) return rc;
     if (!C) return 0;
     const double* dcov = nullptr;
     if ((rc = logwn_gram(c, &dcov, nullptr))) return rc;
@@ -107,7 +80,7 @@ extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double*
     int rc;
     if (!(theta > 0.0) || !std::isfinite(theta))
         return fail(BIOEN_HIP_EINVAL, "bioen_logwn_opt needs theta > 0 (the step divides by theta): use the L-BFGS for theta = 0");
-    if ((rc = logwn_guard(c, __func__))) return rc;
+    if ((rc = dense_guard(c, __func__, kLogwnReasons, fwd_strip_blocks))) return rc;
     if ((rc = enter(c, FX_EVALUATES, __func__))) return rc;
     const double eps = 2.220446049250313e-16;
     ProblemSlot& s0 = c->slot[0];
@@ -119,12 +92,12 @@ extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double*
     BIOEN_HIP_CHECK(hipMemcpyAsync(s0.x, s0.xp, c->ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     BIOEN_HIP_CHECK(hipMemsetAsync(s0.d, 0, c->ld * sizeof(double), c->stream));
     double f = 0.0, ft = 0.0, gmax = 0.0, wmax = 0.0, cmax = 0.0;
-    if ((rc = logwn_eval_point(c, theta, &f, nullptr, __func__))) return rc;
+    if ((rc = logwn_keep_point(c, theta, &f, __func__))) return rc;
     res->evaluations = 1;
     if ((rc = fnewton_buffers(c))) return rc;
-    const LogwGramPlan plan = logw_gram_plan(c);
+    const GramPlan plan = logw_gram_plan(c);
     if ((rc = ensure_scratch(c, SCRATCH_LOGW_GRAM, plan.doubles))) return rc;
-    double* const scal = c->scratch[SCRATCH_LOGW_GRAM].p + plan.vec_at;
+    double* const scal = c->scratch[SCRATCH_LOGW_GRAM].p + plan.tail_at;
     const FNewtonBuf nb = fnewton_layout(c);
     if ((rc = logwn_stats(c, theta, &gmax, &wmax, &cmax))) return rc;
     const int one[1] = {0};
@@ -172,7 +145,7 @@ extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double*
             Round r = make_round(c, one, 1, &alpha, &theta);
             launch_trial(c, r);
             point_drop(c, __func__);
-            if ((rc = logwn_eval_point(c, theta, &ft, nullptr, __func__))) return rc;
+            if ((rc = logwn_keep_point(c, theta, &ft, __func__))) return rc;
             ++res->evaluations;
             at_x = 0;
             if ((rc = logwn_stats(c, theta, &gtmax, &wtmax, &ctmax))) return rc;
@@ -200,7 +173,7 @@ extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double*
     if (!at_x) {                                             // the returned point is the kept one
         BIOEN_HIP_CHECK(hipMemcpyAsync(s0.x, s0.xp, c->ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         point_drop(c, __func__);
-        if ((rc = logwn_eval_point(c, theta, &f, nullptr, __func__))) return rc;
+        if ((rc = logwn_keep_point(c, theta, &f, __func__))) return rc;
         ++res->evaluations;
         if ((rc = logwn_stats(c, theta, &gmax, &wmax, &cmax))) return rc;
     }

@@ -150,7 +150,7 @@ struct ProblemSlot {
 // (api_forces_point.inl: ensure_scratch), kept until the context is destroyed; bioen_hip_ctx_footprint reports buffer i
 // as form 32 << i with its bytes
 enum CtxScratch : int {
-    SCRATCH_GRAM,        // bioen_hip_forces_gram: the sets' partial Gram matrices, their sum, C and H (kernels.hpp: ForcesGramPlan)
+    SCRATCH_GRAM,        // bioen_hip_forces_gram: the sets' partial Gram matrices, their sum, C and H (kernels.hpp: forces_gram_plan)
     SCRATCH_COLQUAD,     // bioen_hip_forces_colquad: P_eff padded to the strip rows, then the n results
     SCRATCH_GRAM16,      // bioen_hip_forces_gram_bf16: the split-BF16 pass's sets, their sum, C~ and H~ -- beside SCRATCH_GRAM,
                          // so that the FP64 pass's results stay what they are
@@ -159,7 +159,7 @@ enum CtxScratch : int {
     SCRATCH_LAPLACE,     // the Laplace error bars (api_forces_laplace.inl): W = L^-1, H^-1, B = W C and C H^-1 C (mp x mp each), then
                          // diag L, diag H^-1 and diag C H^-1 C (mp each)
     SCRATCH_LOGW_GRAM,   // the log-weights dual Newton (api_logw_newton.inl): k_logw_gram's sets, their sum, C, and the loop's scalars
-                         // (kernels.hpp: LogwGramPlan)
+                         // (kernels.hpp: logw_gram_plan)
     SCRATCH_COUNT
 };
 struct CtxScratchBuf {

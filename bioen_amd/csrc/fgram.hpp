@@ -1,15 +1,17 @@
-// What the two dense Hessian passes of the forces method share (kernels_forces_gram.hip, kernels_forces_gram_bf16.hip;
-// DESIGN 6e, 6g): their arguments, the layout of what a set leaves, and everything a wave does that is not arithmetic --
-// which (set, sub-tile) it owns, its rows' centres, the matrix half of a strip's fetch, the row sums on their way out.
-// A kernel keeps what is its own: how the column weights reach a lane, how an operand is formed and multiplied, and which
-// (register, lane) a result leaves from.
+// What the dense Gram passes share (kernels_forces_gram.hip, kernels_forces_gram_bf16.hip, kernels_logw_newton.hip; DESIGN
+// 6e, 6g, 6j): their arguments, the layout of what a set leaves, and everything a wave does that is not arithmetic -- which
+// (set, sub-tile) it owns, its rows' centres, the matrix half of a strip's fetch, the row sums on their way out.
+// The FP64 pass itself is here too, once (fgram_pass): k_forces_gram and k_logw_gram are its two instances, each with a
+// POINT that says how many matrices a wave accumulates and how a column's weights come from what the point keeps.  The
+// BF16 kernel keeps a loop of its own: its weights arrive by shuffles and its operands are split.
 #pragma once
 
 #include "strip.hpp"
 
 namespace bioen {
 
-constexpr int kFGramSubDoubles = 2 * 16 * 4 * 64;      // a sub-tile of both matrices: [matrix 2][h 4][g 4][register 4][lane 64]
+// doubles of a sub-tile of `mats` matrices: [matrix][h 4][g 4][register 4][lane 64]
+__host__ __device__ constexpr int fgram_sub_doubles(int mats) { return mats * 16 * 4 * 64; }
 
 struct FGramArgs {
     const double* Ys;       // row-sum order strip copy
@@ -18,11 +20,11 @@ struct FGramArgs {
     int sps, gs, ilv;       // strips per segment, groups per segment, interleave of the copy
     int nsets;              // local segments x gs
     int nsl, ntiles;        // 64-row slices; 128-row tile pairs I >= J
-    const double* w0;       // the point: prior, x', q - qbar, scalar slot (S_LOGS)
-    const double* x;
+    const double* w0;       // the point -- forces: prior, x', q - qbar, scalar slot (S_LOGS)
+    const double* x;        //           -- log-weights: (w0 unread), e, grad, scalar slot (S_INV + segment)
     const double* qv;
     const double* pscal;
-    double* partial;        // [set][sub-tile (si, sj <= si)][kFGramSubDoubles] | [set][row]: row sums of Y' u2
+    double* partial;        // [set][sub-tile (si, sj <= si)][fgram_sub_doubles] | [set][row]: row sums of Y' u2 | (sum u2)
     size_t set_stride;      // doubles per set
     size_t rows_at;         // where a set's row sums begin
 };
@@ -30,8 +32,14 @@ struct FGramArgs {
 // index of sub-tile (si, sj), sj <= si, among the lower triangle's
 __host__ __device__ inline int fgram_sub(int si, int sj) { return si * (si + 1) / 2 + sj; }
 
+// element (i, j), j <= i, of matrix `mat` among the `mats` of a summed set
+__device__ __forceinline__ double fgram_elem(const double* sum, int mats, int mat, int i, int j) {
+    const int h = (i >> 4) & 3, r = (i & 15) >> 2, lq = i & 3, gb = (j >> 4) & 3, lr = j & 15;
+    return sum[(size_t)fgram_sub(i >> 6, j >> 6) * fgram_sub_doubles(mats) + ((mat * 16 + h * 4 + gb) * 4 + r) * 64 + 16 * lq + lr];
+}
+
 // the copy, the plan's sets in buf, the kept point -- and the grid: a tile pair per set, the tiles of one set on one XCD
-inline FGramArgs fgram_args(const bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
+inline FGramArgs fgram_args(const bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* x, const double* pscal,
                             const double* qv) {
     FGramArgs q{};
     q.Ys = c->Ys[0];
@@ -54,7 +62,7 @@ inline FGramArgs fgram_args(const bioen_hip_ctx* c, const ForcesGramPlan& p, dou
     q.rows_at = p.rows_at;
     return q;
 }
-inline int fgram_blocks(const ForcesGramPlan& p) { return 8 * p.ntiles * ((p.nsets + 7) / 8); }
+inline int fgram_blocks(const GramPlan& p) { return 8 * p.ntiles * ((p.nsets + 7) / 8); }
 
 // A wave's share: the set (segment v, group g: tg strips), the 64-row slices si >= sj whose sub-tile it accumulates, and
 // where the lane's halves of their chunks lie in a strip.
@@ -117,6 +125,117 @@ __device__ __forceinline__ void fgram_store_row_sums(const FGramArgs& q, const F
         const int row = w.ra + 16 * h + lr;
         if (lq == 0) q.partial[(size_t)w.set * q.set_stride + q.rows_at + row] = row < q.mps ? t : 0.0;
     }
+}
+
+// ---- the FP64 pass -------------------------------------------------------------------------------------------------------
+// A wave's 64-row slice of a strip arrives as 8 chunks whose halves ARE operands of v_mfma_f64_16x16x4_f64 (row = lane & 15,
+// k = lane >> 4) -- as A for its own row block and, the same registers of another slice, as B: G'_IJ += Y'_I diag(u) Y'_J^T
+// with no transpose and no LDS image.  A wave owns a 64 x 64 sub-tile of Point::kMats matrices (16 accumulators of 4 doubles
+// each), matrix 0 weighted by u1, matrix 1 by u2; the row sums of Y' u2 ride along, and with Point::kSumU2 sum u2 itself.
+// A Point holds the strip's per-column registers (columns 4 qq + (lane >> 4), qq = 0 .. 3) and supplies
+//   static double scalar(q, w)                 the wave's scalar of the point
+//   void load(q, col)                          its registers from the point's vectors
+//   void weights(scalar, qq, valid, u1, u2)    a column's two weights; `valid`: the column lies below n
+template <class Point>
+struct FGramRegs {
+    d2 a[kWaveRows / 8];
+    d2 b[kWaveRows / 8];
+    Point pt;
+};
+
+template <class Point>
+__device__ __forceinline__ void fgram_pass(const FGramArgs& q) {
+    constexpr int kMats = Point::kMats;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lq = lane >> 4, lr = lane & 15;
+    FGramWave w;
+    if (!fgram_decode(q, lane, wave, w)) return;
+    const double scal = Point::scalar(q, w);
+    double ca[4], cb[4];                            // the centres of the lane's rows
+    fgram_centres(q, w, lr, ca, cb);
+
+    auto fetch = [&](int i, FGramRegs<Point>& r) {
+        const int s = fgram_strip(q, w, i);
+        fgram_fetch(q, w, s, r.a, r.b);
+        r.pt.load(q, (size_t)s * kStripCols + lq);
+    };
+
+    d4 acc[kMats][4][4];                            // [matrix][row block of slice si][row block of slice sj]
+    double rs[4], sg = 0.0;                         // the lane's share of the row sums of Y' u2 (slice si), of sum u2
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        rs[h] = 0.0;
+#pragma unroll
+        for (int gb = 0; gb < 4; ++gb)
+#pragma unroll
+            for (int mat = 0; mat < kMats; ++mat) acc[mat][h][gb] = d4{0.0, 0.0, 0.0, 0.0};
+    }
+
+    // One register set: a strip's operands are centred into registers of their own (and its weights formed) as soon as it
+    // has arrived, the set is then refilled with the NEXT strip, which travels while this one is multiplied (64 matrix
+    // instructions of 64 cycles each per matrix: longer than any load).
+    FGramRegs<Point> pre;
+    fetch(0, pre);
+#pragma unroll 1
+    for (int i = 0; i < w.tg; ++i) {
+        const size_t col0 = (size_t)fgram_strip(q, w, i) * kStripCols + lq;
+        double u1[4], u2[4];
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) {
+            pre.pt.weights(scal, qq, col0 + 4 * qq < (size_t)q.n, u1[qq], u2[qq]);
+            if constexpr (Point::kSumU2) sg += u2[qq];
+        }
+        double ac[4][4], bc[4][4];                  // [column quad][row block]
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                const d2 av = pre.a[2 * h + (qq >> 1)], bv = pre.b[2 * h + (qq >> 1)];
+                ac[qq][h] = ((qq & 1) ? av.y : av.x) - ca[h];
+                bc[qq][h] = ((qq & 1) ? bv.y : bv.x) - cb[h];
+            }
+        fetch(i + 1 < w.tg ? i + 1 : i, pre);       // unconditional
+        asm volatile("" ::: "memory");              // the loads are issued HERE, in front of the products (the compiler sank them behind)
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) {
+            double bu[kMats][4];
+#pragma unroll
+            for (int gb = 0; gb < 4; ++gb) {
+                bu[0][gb] = bc[qq][gb] * u1[qq];
+                if constexpr (kMats == 2) bu[1][gb] = bc[qq][gb] * u2[qq];
+            }
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                rs[h] = fma(ac[qq][h], u2[qq], rs[h]);
+#pragma unroll
+                for (int gb = 0; gb < 4; ++gb)
+#pragma unroll
+                    for (int mat = 0; mat < kMats; ++mat)
+                        acc[mat][h][gb] = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[qq][h], bu[mat][gb], acc[mat][h][gb], 0, 0, 0);
+            }
+        }
+    }
+
+    // The set leaves, accumulator by accumulator as the registers hold it: result register r of lane 16 lq + lr is row
+    // 4 r + lq, column lr of the 16 x 16 block (fgram_elem).  Row blocks beyond the strip's last one were redirected to the
+    // slice's first (strip_chunk_offsets): what they leave lies beyond row m of the matrices and is never read.
+    double* const set = q.partial + (size_t)w.set * q.set_stride;
+    double* const dst = set + (size_t)fgram_sub(w.si, w.sj) * fgram_sub_doubles(kMats) + lane;
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+        for (int gb = 0; gb < 4; ++gb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int mat = 0; mat < kMats; ++mat) dst[((mat * 16 + h * 4 + gb) * 4 + r) * 64] = acc[mat][h][gb][r];
+    fgram_store_row_sums(q, w, lq, lr, rs);
+    if constexpr (Point::kSumU2)
+        if (w.si == 0) {                            // (sj = 0 too) over the set's columns: the four quarters hold four columns each
+            const double t = quad_sum(sg);
+            if (lane == 0) set[q.rows_at + (size_t)q.nsl * kWaveRows] = t;
+        }
 }
 
 }  // namespace bioen

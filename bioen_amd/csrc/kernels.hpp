@@ -189,36 +189,31 @@ void launch_forces_colsum(bioen_hip_ctx* c, const double* u_c, double* out);    
 
 // ---- dense Hessian and covariance of the forces objective in one pass (kernels_forces_gram.hip; what its
 // kernel shares with the BF16 pass's: fgram.hpp) ---------------------------------------------------------------------------
-struct ForcesGramPlan {
+struct GramPlan {                   // the sets of a dense Gram pass and what lies behind them, both methods' 
     int nsl, ntiles, nsub;          // 64-row slices, 128-row tile pairs I >= J, 64 x 64 sub-tiles of the lower triangle
     int gs, nsets;                  // groups per canonical segment; sets of this context (local segments x gs)
-    size_t set_stride, rows_at;     // doubles per set; where a set's row sums begin
-    size_t cov_at, hess_at;         // behind the sets and their sum: C and H, m x m each
+    size_t set_stride, rows_at;     // doubles per set; where a set's row sums begin (log-weights: behind them, sum grad)
+    size_t cov_at, tail_at;         // behind the sets and their sum: C (m x m), then forces: H (m x m); log-weights: kLogwnScal scalars
     size_t doubles;                 // the whole buffer
 };
-ForcesGramPlan forces_gram_plan(const bioen_hip_ctx* c);
-void launch_forces_gram(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
+// mats: matrices per sub-tile; set_extra: doubles of a set behind its row sums; tail: doubles behind C
+GramPlan gram_plan(const bioen_hip_ctx* c, int mats, int set_extra, size_t tail);
+GramPlan forces_gram_plan(const bioen_hip_ctx* c);
+void launch_forces_gram(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* x, const double* pscal,
                         const double* qv, const double* ybar, double theta);
 // what follows the sets, whichever kernel has written them: their sum in its fixed order, the rank corrections, + C C
 // (k_fgram_sum_sets, k_fgram_finish, k_fgram_square, defined in kernels_forces_gram.hip)
-void launch_fgram_tail(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* ybar, double theta);
+void launch_fgram_tail(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* ybar, double theta);
 
 void launch_fgram_sum_sets(bioen_hip_ctx* c, double* buf, size_t set_stride, int nlocal, int gs);   // the sets' sum alone, behind them
 
 // ---- the log-weights method's dual Newton step (kernels_logw_newton.hip): the covariance of the observables
 // under the weights of the kept log-weights point, ONE M x M x N product on the copy the forward pass reads, and the
 // vector kernels of the loop around it --------------------------------------------------------------------------------
-struct LogwGramPlan {
-    int nsl, ntiles, nsub;          // as ForcesGramPlan's
-    int gs, nsets;
-    size_t set_stride, rows_at;     // doubles per set; where a set's row sums of Y' grad begin (behind them: sum grad)
-    size_t cov_at, vec_at;          // behind the sets and their sum: C (m x m), then kLogwnScal scalars
-    size_t doubles;
-};
 enum LogwnScal : int { LN_GMAX = 0, LN_WMAX, LN_GAMMA, LN_SLOPE, kLogwnScal = 8 };
-LogwGramPlan logw_gram_plan(const bioen_hip_ctx* c);
+GramPlan logw_gram_plan(const bioen_hip_ctx* c);
 // the sets, their sum, C (affine model: S C S) at buf + cov_at; negb (may be NULL, mp doubles) <- -Yc grad (affine: S .)
-void launch_logw_gram(bioen_hip_ctx* c, const LogwGramPlan& p, double* buf, const double* e, const double* grad,
+void launch_logw_gram(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* e, const double* grad,
                       const double* pscal, const double* ybar, double* negb);
 // operand <- r_c + row_scale o z (K = 1: the centred adjoint's operand), its constants S_B0, S_UY into scal
 void launch_logwn_operand(bioen_hip_ctx* c, const double* z, double* scal);
@@ -231,7 +226,7 @@ void launch_logwn_step(bioen_hip_ctx* c, const double* x, const double* cadj, co
 
 // the same pass with split-BF16 operands on the BF16 matrix cores (kernels_forces_gram_bf16.hip): the plan, the
 // sets' layout and the tail are the FP64 pass's, buf is a buffer of its own
-void launch_forces_gram_bf16(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
+void launch_forces_gram_bf16(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* x, const double* pscal,
                              const double* qv, const double* ybar, double theta);
 
 // ---- dense FP64 Cholesky factorisation and solves on the device, M <= 1024 (kernels_forces_newton.hip) --------

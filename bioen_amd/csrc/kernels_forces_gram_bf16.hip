@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGramArgs q) {
     // (i & 15) >> 2 of lane 16 (i & 3) + j).  Result register r of lane 16 lq + lr of THIS instruction is row 4 lq + r,
     // column lr of the block: it goes to register slot lq, lane 16 r + lr.  Row blocks beyond the strip's last one were
     // redirected (strip_chunk_offsets): what they leave lies beyond row m and is never read (k_fgram_finish).
-    double* const dst = q.partial + (size_t)w.set * q.set_stride + (size_t)fgram_sub(w.si, w.sj) * kFGramSubDoubles + lr;
+    double* const dst = q.partial + (size_t)w.set * q.set_stride + (size_t)fgram_sub(w.si, w.sj) * fgram_sub_doubles(2) + lr;
 #pragma unroll
     for (int h = 0; h < 4; ++h)
 #pragma unroll
@@ -149,8 +149,8 @@ __global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGramArgs q) {
 
 // ---- host side ------------------------------------------------------------------------------------
 // buf: forces_gram_plan's doubles (a buffer of this entry's own); x, pscal, qv, ybar: the kept point's.  Leaves C~ at
-// buf + cov_at, H~ at buf + hess_at.
-void launch_forces_gram_bf16(bioen_hip_ctx* c, const ForcesGramPlan& p, double* buf, const double* x, const double* pscal,
+// buf + cov_at, H~ at buf + tail_at.
+void launch_forces_gram_bf16(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* x, const double* pscal,
                              const double* qv, const double* ybar, double theta) {
     hipLaunchKernelGGL(k_forces_gram_bf16, dim3(fgram_blocks(p)), dim3(256), 0, c->stream,
                        fgram_args(c, p, buf, x, pscal, qv));

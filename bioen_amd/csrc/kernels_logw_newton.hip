@@ -4,12 +4,13 @@
 //   C      = G' - ybar' ybar'^T                          the covariance of the observables under the weights
 //   b      = sum_j grad_j Y'_j - ybar' sum_j grad_j      = Yc grad, the right-hand side of (C + theta I) z = -b
 //   (affine model, S = diag(row_scale): C_A = S C S, b_A = S b)
-// k_logw_gram is k_forces_gram (kernels_forces_gram.hip) with ONE matrix: the same copy -- the row-sum order strip copy the
-// log-weights forward pass reads, in whichever layout it is (strip_phys) --, the same decode, centres, fetch, sets and
-// row sums (fgram.hpp), half the matrix instructions and half the accumulators (128 AGPRs + 224 VGPRs, no scratch; one
-// wave per SIMD as there: with two, in 256 registers, the compiler spills 23 of them).  A wave owns a 64 x 64 sub-tile; the weights are slot 0's e times the softmax factor of the set's segment (S_INV), columns
-// beyond n weigh nothing; the row sums ride along with u = grad.  One writer per (set, sub-tile), the sets added by
-// k_fgram_sum_sets in its fixed order, C finished on the lower triangle and mirrored: bitwise symmetric.
+// k_logw_gram is fgram.hpp's FP64 pass (fgram_pass: k_forces_gram's, kernels_forces_gram.hip) at the log-weights point, with
+// ONE matrix: the same copy -- the row-sum order strip copy the log-weights forward pass reads, in whichever layout it is
+// (strip_phys) --, the same decode, centres, fetch, loop, sets and row sums, half the matrix instructions and half the
+// accumulators (128 AGPRs + 224 VGPRs, no scratch; one wave per SIMD as there: with two, in 256 registers, the compiler
+// spills 23 of them).  A wave owns a 64 x 64 sub-tile; the row sums ride along with u = grad, and so does sum grad.  One
+// writer per (set, sub-tile), the sets added by k_fgram_sum_sets in its fixed order, C finished on the lower triangle and
+// mirrored: bitwise symmetric.
 // Around it the N-vector kernels of the loop, on the k_hessp_* pattern (kernels_hessp.hip): block partials into the X_GRAD
 // stage, met in segment order by a one-block kernel.  The entries that launch them serve unsharded contexts only: the
 // stage is not exchanged.
@@ -17,105 +18,27 @@
 
 namespace bioen {
 
-constexpr int kLGramSubDoubles = 16 * 4 * 64;          // a sub-tile: [h 4][g 4][register 4][lane 64]
-
-struct LGramRegs {
-    d2 a[kWaveRows / 8];
-    d2 b[kWaveRows / 8];
-    double e[4], gr[4];              // the strip's columns 4 qq + (lane >> 4), qq = 0 .. 3
+// The log-weights point, in FGramArgs x = e, qv = grad, pscal = the point's scalar slot, w0 unread: the weights are slot 0's
+// e times the softmax factor of the set's segment (S_INV), u2 = grad; columns beyond n weigh nothing
+struct LogwGramPoint {
+    static constexpr int kMats = 1;
+    static constexpr bool kSumU2 = true;
+    double e[4], gr[4];
+    __device__ __forceinline__ static double scalar(const FGramArgs& q, const FGramWave& w) { return q.pscal[S_INV + w.v]; }
+    __device__ __forceinline__ void load(const FGramArgs& q, size_t col) {
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) {
+            e[qq] = q.x[col + 4 * qq];
+            gr[qq] = q.qv[col + 4 * qq];
+        }
+    }
+    __device__ __forceinline__ void weights(double inv, int qq, bool valid, double& u1, double& u2) const {
+        u1 = valid ? e[qq] * inv : 0.0;
+        u2 = valid ? gr[qq] : 0.0;
+    }
 };
 
-// FGramArgs as this kernel reads them: x = e, qv = grad, pscal = the point's scalar slot (S_INV), w0 unused
-__global__ __launch_bounds__(256, 1) void k_logw_gram(FGramArgs q) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lq = lane >> 4, lr = lane & 15;
-    FGramWave w;
-    if (!fgram_decode(q, lane, wave, w)) return;
-    const double inv = q.pscal[S_INV + w.v];        // w_j = e_j inv in the set's segment
-    double ca[4], cb[4];
-    fgram_centres(q, w, lr, ca, cb);
-
-    auto fetch = [&](int i, LGramRegs& r) {
-        const int s = fgram_strip(q, w, i);
-        fgram_fetch(q, w, s, r.a, r.b);
-        const size_t col = (size_t)s * kStripCols + lq;
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-            r.e[qq] = q.x[col + 4 * qq];
-            r.gr[qq] = q.qv[col + 4 * qq];
-        }
-    };
-
-    d4 acc[4][4];                                   // [row block of slice si][row block of slice sj]
-    double rs[4], sg = 0.0;                         // the lane's share of the row sums of Y' grad (slice si), of sum grad
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        rs[h] = 0.0;
-#pragma unroll
-        for (int gb = 0; gb < 4; ++gb) acc[h][gb] = d4{0.0, 0.0, 0.0, 0.0};
-    }
-
-    LGramRegs pre;                                  // one register set, refilled with the NEXT strip while this one is multiplied
-    fetch(0, pre);
-#pragma unroll 1
-    for (int i = 0; i < w.tg; ++i) {
-        const size_t col0 = (size_t)fgram_strip(q, w, i) * kStripCols + lq;
-        double u1[4], u2[4];
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-            const bool valid = col0 + 4 * qq < (size_t)q.n;
-            u1[qq] = valid ? pre.e[qq] * inv : 0.0;
-            u2[qq] = valid ? pre.gr[qq] : 0.0;
-            sg += u2[qq];
-        }
-        double ac[4][4], bc[4][4];                  // [column quad][row block]
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq)
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                const d2 av = pre.a[2 * h + (qq >> 1)], bv = pre.b[2 * h + (qq >> 1)];
-                ac[qq][h] = ((qq & 1) ? av.y : av.x) - ca[h];
-                bc[qq][h] = ((qq & 1) ? bv.y : bv.x) - cb[h];
-            }
-        fetch(i + 1 < w.tg ? i + 1 : i, pre);       // unconditional
-        asm volatile("" ::: "memory");              // the loads are issued HERE, in front of the products
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-            double b1[4];
-#pragma unroll
-            for (int gb = 0; gb < 4; ++gb) b1[gb] = bc[qq][gb] * u1[qq];
-#pragma unroll
-            for (int h = 0; h < 4; ++h) {
-                rs[h] = fma(ac[qq][h], u2[qq], rs[h]);
-#pragma unroll
-                for (int gb = 0; gb < 4; ++gb)
-                    acc[h][gb] = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[qq][h], b1[gb], acc[h][gb], 0, 0, 0);
-            }
-        }
-    }
-
-    // result register r of lane 16 lq + lr is row 4 r + lq, column lr of the 16 x 16 block (as k_forces_gram leaves it)
-    double* const set = q.partial + (size_t)w.set * q.set_stride;
-    double* const dst = set + (size_t)fgram_sub(w.si, w.sj) * kLGramSubDoubles + lane;
-#pragma unroll
-    for (int h = 0; h < 4; ++h)
-#pragma unroll
-        for (int gb = 0; gb < 4; ++gb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dst[((h * 4 + gb) * 4 + r) * 64] = acc[h][gb][r];
-    fgram_store_row_sums(q, w, lq, lr, rs);
-    if (w.si == 0) {                                // (sj = 0 too) sum grad over the set's columns: the four quarters hold four columns each
-        const double t = quad_sum(sg);
-        if (lane == 0) set[q.rows_at + (size_t)q.nsl * kWaveRows] = t;
-    }
-}
-
-// element (i, j), j <= i, of the summed set
-__device__ __forceinline__ double lgram_elem(const double* sum, int i, int j) {
-    const int h = (i >> 4) & 3, r = (i & 15) >> 2, lq = i & 3, gb = (j >> 4) & 3, lr = j & 15;
-    return sum[(size_t)fgram_sub(i >> 6, j >> 6) * kLGramSubDoubles + ((h * 4 + gb) * 4 + r) * 64 + 16 * lq + lr];
-}
+__global__ __launch_bounds__(256, 1) void k_logw_gram(FGramArgs q) { fgram_pass<LogwGramPoint>(q); }
 
 // The rank correction and the affine model's scales on the lower triangle, mirrored; the blocks of tile column 0 also leave
 // -b for the solve.  16 x 16 threads per block, blocks above the diagonal leave.
@@ -127,7 +50,7 @@ __global__ __launch_bounds__(256) void k_lgram_finish(const double* __restrict__
     const int i = blockIdx.y * 16 + (threadIdx.x >> 4), j = blockIdx.x * 16 + (threadIdx.x & 15);
     if (i >= m || j > i) return;
     const double yi = ybar[i] - center[i], yj = ybar[j] - center[j];
-    double cv = fma(-yi, yj, lgram_elem(sum, i, j));
+    double cv = fma(-yi, yj, fgram_elem(sum, 1, 0, i, j));
     if (affine) cv = (row_scale[i] * cv) * row_scale[j];
     cov[(size_t)i * m + j] = cv;
     cov[(size_t)j * m + i] = cv;
@@ -241,47 +164,12 @@ __global__ __launch_bounds__(kBlock) void k_logwn_step_finish(Xch xi, double* __
 }
 
 // ---- host side ------------------------------------------------------------------------------------
-// forces_gram_plan's sets (gs: enough of them for two blocks per CU over the canonical segments' tiles -- a function of
-// (segcols, M) alone) with one matrix per sub-tile
-LogwGramPlan logw_gram_plan(const bioen_hip_ctx* c) {
-    LogwGramPlan p{};
-    const int mps = panel_mps(c, 0);
-    p.nsl = (mps + kWaveRows - 1) / kWaveRows;
-    const int t = (p.nsl + 1) / 2;
-    p.ntiles = t * (t + 1) / 2;
-    p.nsub = p.nsl * (p.nsl + 1) / 2;
-    const int sps = strip_sps(c);
-    p.gs = std::max(1, std::min(sps, (512 + c->nseg * p.ntiles - 1) / (c->nseg * p.ntiles)));
-    p.nsets = c->vr * p.gs;
-    p.rows_at = (size_t)p.nsub * kLGramSubDoubles;
-    p.set_stride = p.rows_at + (size_t)p.nsl * kWaveRows + 8;      // the row sums, then sum grad
-    p.cov_at = (size_t)(p.nsets + 1) * p.set_stride;
-    p.vec_at = p.cov_at + (size_t)c->m * c->m;
-    p.doubles = p.vec_at + kLogwnScal;
-    return p;
-}
+// gram_plan's sets with one matrix per sub-tile; behind a set's row sums sum grad (8 doubles), behind C the loop's scalars
+GramPlan logw_gram_plan(const bioen_hip_ctx* c) { return gram_plan(c, 1, 8, kLogwnScal); }
 
-void launch_logw_gram(bioen_hip_ctx* c, const LogwGramPlan& p, double* buf, const double* e, const double* grad,
+void launch_logw_gram(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* e, const double* grad,
                       const double* pscal, const double* ybar, double* negb) {
-    FGramArgs q{};
-    q.Ys = c->Ys[0];
-    q.center = c->strip_center;
-    q.mps = panel_mps(c, 0);
-    q.mp = c->mp;
-    q.n = c->n;
-    q.sps = strip_sps(c);
-    q.gs = p.gs;
-    q.ilv = strip_ilv(c);
-    q.nsets = p.nsets;
-    q.nsl = p.nsl;
-    q.ntiles = p.ntiles;
-    q.x = e;
-    q.qv = grad;
-    q.pscal = pscal;
-    q.partial = buf;
-    q.set_stride = p.set_stride;
-    q.rows_at = p.rows_at;
-    hipLaunchKernelGGL(k_logw_gram, dim3(8 * p.ntiles * ((p.nsets + 7) / 8)), dim3(256), 0, c->stream, q);
+    hipLaunchKernelGGL(k_logw_gram, dim3(fgram_blocks(p)), dim3(256), 0, c->stream, fgram_args(c, p, buf, e, pscal, grad));
     launch_fgram_sum_sets(c, buf, p.set_stride, c->vr, p.gs);
     const double* sum = buf + (size_t)p.nsets * p.set_stride;
     const int tb = (c->m + 15) / 16;

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """SHA-256 of the bytes of every output of the dense forces entries (forces_gram, forces_gram_bf16, forces_colquad,
-opt_newton_forces, forces_newton_factor / _solve, forces_inverse, forces_laplace) on seeded synthetic
-contexts, as JSON: two builds of the library that print the same digests compute the same bits.
+opt_newton_forces, forces_newton_factor / _solve, forces_inverse, forces_laplace) and of the log-weights
+dense entries (logw_cov, opt_dual_newton_logw, with logw_hessp at their point) on seeded synthetic contexts, as
+JSON: two builds of the library that print the same digests compute the same bits.
 
     python3 tools/forces_dense_digest.py > new.json
     BIOEN_HIP_LIBRARY=/path/to/other/libbioen_hip.so python3 tools/forces_dense_digest.py > old.json
@@ -85,6 +86,19 @@ def run_case(case):
             out["forces_newton_factor(indefinite)"] = sha("none" if L is None else L, info)
             out["info_indefinite"] = info
             out["newton_status"] = res["status"]
+            # the log-weights dense entries, on the same context (draws of their own: the digests above stay what they were)
+            lrng = np.random.default_rng(M * N + 1)
+            G = np.log(w0)
+            g = G + 0.1 * lrng.standard_normal(N)
+            out["logw_cov(g)"] = sha(*ctx.logw_cov(g=g, G=G, theta=THETA))
+            out["logw_cov()"] = sha(ctx.logw_cov())
+            V = lrng.standard_normal((8, N))
+            out["logw_hessp(k=1)"] = sha(ctx.logw_hessp(V[0]))
+            out["logw_hessp(k=8)"] = sha(ctx.logw_hessp(V))
+            dn = ctx.opt_dual_newton_logw(g, G, THETA, dict(gtol=1e-8))
+            out["opt_dual_newton_logw"] = sha(*(dn[k] for k in sorted(dn)))
+            out["logw_cov() at the optimum"] = sha(ctx.logw_cov())
+            out["dual_newton_status"] = dn["status"]
     finally:
         if segments is None:
             os.environ.pop("BIOEN_HIP_SEGMENTS", None)
