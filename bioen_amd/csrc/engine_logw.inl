@@ -12,6 +12,7 @@ struct BatchProblem {
     bool need_direction = false; // build d before the next trial
     bool accept = false;         //   ... after committing the (s, y) pair
     int end = 0, bound = 0;
+    int last_dir = 0, prev_dir = 0; // the running line search's last two moves: -1 step decreased, +1 increased, 0 none yet
     std::chrono::steady_clock::time_point t0;
 };
 
@@ -23,8 +24,17 @@ struct LogwBatchEngine {
     bool speculate = true;
     int max_shadows = 2;                             // shadow evaluations per round at most (BIOEN_HIP_HOST_SHADOWS): both
                                                      // steps of the slowest problem (r02: every idle slot)
-    bool shadow_mixed_first = false;                 // third candidate of a search: the up-then-down step instead of stp / 4
+    bool shadows_fixed = false;                      // ... given by the caller: holds in every round, the opening included
     long long spec_launched = 0, spec_used = 0;      // shadow evaluations issued / adopted
+
+    // The opening of a series (see run): while the slowest active problem has accepted fewer than kOpeningIterations
+    // steps -- and for kOpeningRounds rounds at most, which is all a series pays whose smallest theta is not its slowest
+    // member -- all free slots shadow it, and a series that fills the batch keeps kOpeningReserve slots back instead of two.
+    // Headline (profiles/r18_opening_lattice.txt): 15 of the 19 rejections of the slowest theta that two shadows leave
+    // uncovered fall into its iterations 0 ... 3, which take 10 rounds with five shadows (20 with two).
+    static constexpr int kOpeningReserve = 5;
+    static constexpr int kOpeningIterations = 4;
+    static constexpr int kOpeningRounds = 24;
 
     // Deliveries: the optimum and the weights of a finished problem (2 N doubles into the caller's pageable arrays,
     // 1.5 ms at N = 1e6) leave on a second stream, driven by a helper thread that blocks in the copy while this
@@ -45,8 +55,10 @@ struct LogwBatchEngine {
         : c(ctx), cfg(config), verbose(verb) {
         const char* e = std::getenv("BIOEN_HIP_SPECULATE");
         speculate = !(e && e[0] == '0');
-        if (const char* m = std::getenv("BIOEN_HIP_HOST_SHADOWS")) max_shadows = std::max(0, std::min((int)kMaxBatch, std::atoi(m)));
-        if (const char* m = std::getenv("BIOEN_HIP_SHADOW_MIXED")) shadow_mixed_first = m[0] == '1';
+        if (const char* m = std::getenv("BIOEN_HIP_HOST_SHADOWS")) {
+            max_shadows = std::max(0, std::min((int)kMaxBatch, std::atoi(m)));
+            shadows_fixed = true;
+        }
         const char* d = std::getenv("BIOEN_HIP_DELIVERY");
         async_delivery = !(d && d[0] == '0');
         if (const char* j = std::getenv("BIOEN_HIP_JITTER_US")) jitter_us = std::max(0, std::atoi(j));
@@ -360,14 +372,21 @@ struct LogwBatchEngine {
         // search rejects most in its first iterations (the headline's slowest theta: 19 of 39 rejected trials in the
         // first 13 rounds).  Such a series keeps two slots back for shadows of the slowest problem from the first
         // round on; the two fastest thetas wait for the first slots to come free (they need a fraction of the rounds).
+        // During the opening (kOpeningIterations, kOpeningRounds above) kOpeningReserve slots are kept back: kp problem
+        // slots then, kb after it.  BIOEN_HIP_RESERVE=r keeps r slots back from the first round to the last, and so does a
+        // caller who fixes the shadows per round (BIOEN_HIP_HOST_SHADOWS): both as they were before there was an opening.
         std::vector<int> start_order(ntheta);
         for (int i = 0; i < ntheta; ++i) start_order[i] = i;
         std::stable_sort(start_order.begin(), start_order.end(), [&](int x, int y) { return theta_before(thetas[x], thetas[y]); });
         const bool backtracking = cfg.linesearch >= 1 && cfg.linesearch <= 3;
+        int kp = kb;                 // problem slots now
         if (speculate && backtracking && max_shadows >= 2 && kb == kMaxBatch && ntheta <= kMaxBatch) {
             const char* e = std::getenv("BIOEN_HIP_RESERVE");
             kb -= e ? std::max(0, std::min(4, std::atoi(e))) : 2;
+            kp = (e || shadows_fixed) ? kb : std::min(kb, kMaxBatch - kOpeningReserve);
         }
+        bool opening = speculate && backtracking && !shadows_fixed;     // (any series: all its free slots shadow the slowest problem)
+        int rounds = 0;
         for (int s = 0; s < kb; ++s) note(alloc_slot(c, s, true));
         if (rc) return rc;
         // cache policy of the round's N-vector kernels (kernels_logw.hip): nontemporal history loads and outputs once the
@@ -474,18 +493,32 @@ struct LogwBatchEngine {
             --active;
         };
 
-        for (int s = 0; s < kb && next < ntheta; ++s) start_problem(s);
+        for (int s = 0; s < kp && next < ntheta; ++s) start_problem(s);
 
         // The evaluation-owned entries of a slot's scalars (the rest -- y.s, alpha, gp.d -- belongs to the problem)
         static const int kEvalScal[][2] = {{S_F, 4}, {S_LOGS, 4}, {S_KL, 2}, {S_INV, kMaxSeg + 2}};      // (S_INV[kMaxSeg], S_B0, S_UY)
 
         while (active > 0 && !rc) {
             jitter(1);
+            if (opening) {
+                // Over once the slowest active problem has left its first iterations behind, or after kOpeningRounds: the
+                // problems kept back for it start in the slots that served as shadows.  Decided from the machines' states
+                // and the round count alone: every rank of a sharded run composes the same rounds.
+                int slow = -1;
+                for (int s = 0; s < kp; ++s)
+                    if (occupied[s] && (slow < 0 || theta_before(slots[s].theta, slots[slow].theta))) slow = s;
+                if (rounds >= kOpeningRounds || slow < 0 || slots[slow].machine->iterations() >= kOpeningIterations) {
+                    opening = false;
+                    for (int s = kp; s < kb && next < ntheta; ++s) start_problem(s);
+                    kp = kb;
+                }
+            }
+            ++rounds;
             // ---- one round: every active problem evaluates its next point -------------------------
             int list[kMaxBatch];
             double stp[kMaxBatch], th[kMaxBatch];
             int k = 0;
-            for (int s = 0; s < kb; ++s) {
+            for (int s = 0; s < kp; ++s) {
                 if (!occupied[s]) continue;
                 list[k] = s;
                 stp[k] = slots[s].initial ? 0.0 : slots[s].machine->trial_step();
@@ -500,42 +533,39 @@ struct LogwBatchEngine {
             int shadow_owner[kMaxBatch], shadow_slot[kMaxBatch];
             double shadow_stp[kMaxBatch];
             int nshadow = 0;
-            if (speculate && (nslots > kb || active < kb)) {
+            int nfree0 = 0;                          // (diagnostics: free slots when the round was composed)
+            if (speculate && (nslots > kp || active < kp)) {
                 int free_slots[kMaxBatch], nfree = 0;
                 for (int s = 0; s < nslots; ++s)
-                    if ((s >= kb || !occupied[s]) && !slot_blocked(s)) free_slots[nfree++] = s;
+                    if ((s >= kp || !occupied[s]) && !slot_blocked(s)) free_slots[nfree++] = s;
+                nfree0 = nfree;
                 // Who gets the idle slots: the series ends when its SLOWEST member does, so a saved evaluation shortens it
                 // only on that member's path -- the smallest theta in every series measured (r03; r02 dealt stp / 2 to
                 // everybody first and reached the straggler last: 22 of its 45 rejected trials saved at the headline).
-                // Owners in ascending theta, both steps each, while slots last.
+                // Owners in ascending theta, both first-level steps each, while slots last and max_shadows is not reached;
+                // during the opening the slowest owner takes every free slot.
                 int order[kMaxBatch];
                 for (int a = 0; a < k; ++a) order[a] = a;
                 std::sort(order, order + k, [&](int x, int y) { return theta_before(th[x], th[y]); });
-                for (int i = 0; i < k && nfree > 0 && nshadow < max_shadows; ++i) {
+                for (int i = 0; i < k && nfree > 0; ++i) {
+                    const int limit = (opening && i == 0) ? (int)kMaxBatch : max_shadows;
+                    if (nshadow >= limit) break;
                     const int a = order[i];
                     BatchProblem& p = slots[list[a]];
-                    // The steps the search can ask for after this trial -- formed exactly as report_backtracking forms
-                    // them (lbfgs.c:686-727): stp * 0.5 | stp * 2.1 -- and, should slots remain, the ones a rejected
-                    // successor would ask for.  (Measured at the headline, r03: the two first-level steps for the slowest
-                    // theta catch every first rejection, 29 of its 45 extra evaluations.  The other 16 are second rejections
-                    // inside one search -- r04, BIOEN_HIP_SPEC_DEBUG: 4 x "up again" in the first search, 6 x "up, then down"
-                    // in one ping-pong search around evaluation 20, 6 x "down again" -- all but one within the first 36
-                    // evaluations, when the two reserved slots are the only free ones: a third candidate would need a third
-                    // theta to wait, for at most 5-6 of 406 rounds.)
-                    double c1[2], cand[5];
-                    int nc = p.initial ? 0 : p.machine->speculative_steps(c1);
-                    for (int i2 = 0; i2 < nc; ++i2) cand[i2] = c1[i2];
-                    if (nc == 2) {
-                        cand[2] = c1[0] * 0.5;
-                        cand[3] = c1[1] * 2.1;
-                        cand[4] = c1[1] * 0.5;           // up, then down (= down, then up: the halving is exact)
-                        nc = 5;
-                        if (shadow_mixed_first) std::swap(cand[2], cand[4]);
-                    } else if (nc == 1) {
-                        cand[1] = c1[0] * 0.5;
-                        nc = 2;
-                    }
-                    for (int pass = 0; pass < nc && nfree > 0 && nshadow < max_shadows; ++pass) {
+                    // The steps the search can ask for after this trial and, should slots remain, after its successors --
+                    // lb::speculative_lattice: formed exactly as report_backtracking forms them (lbfgs.c:686-727), the two
+                    // first-level steps first, then the chain of the search's habit, then the rest of the second level.
+                    // Measured at the headline (profiles/r18_opening_lattice.txt, BIOEN_HIP_SPEC_DEBUG): with two shadows
+                    // the first-level steps catch every first rejection of the slowest theta, 39 of its 58 rejected
+                    // trials.  The other 19 are later rejections inside one search and cost a round each.  15 of them
+                    // fall into its first four searches (37 evaluations): the first multiplies 1 / |g| up nine times,
+                    // the second halves four times and then goes up and down in turn twelve times, the next two halve
+                    // five and two times.  With five shadows on the lattice those searches take 2 + 4 + 2 + 1 rounds
+                    // instead of 5 + 9 + 3 + 2: 481 rounds instead of 491.  The last four (evaluations 203 ... 210)
+                    // lie outside the opening and stay.
+                    double cand[lb::kLatticeMax];
+                    const int nc = p.initial ? 0 : p.machine->speculative_lattice(p.last_dir, p.prev_dir, std::min(nfree, limit - nshadow), cand);
+                    for (int pass = 0; pass < nc; ++pass) {
                         note(alloc_slot(c, free_slots[nfree - 1], false));
                         shadow_owner[nshadow] = a;
                         shadow_slot[nshadow] = free_slots[--nfree];
@@ -598,33 +628,31 @@ struct LogwBatchEngine {
                 } else {
                     TrialResult t{h[S_F], h[S_DG], h[S_GG], h[S_XX], h[S_DGINIT]};
                     act = p.machine->on_trial(t);
-                    if (act.kind == LbfgsMachine::TRIAL && dbg) {
-                        int mine = 0, hit = 0;
-                        for (int q = 0; q < nshadow; ++q)
-                            if (shadow_owner[q] == a) { ++mine; hit += shadow_stp[q] == p.machine->trial_step(); }
-                        ++dbg_rej[p.id];
-                        if (!mine) ++dbg_noslot[p.id]; else if (!hit) ++dbg_miss[p.id];
-                        if (!hit) {
-                            std::fprintf(stderr, "spec debug: theta %g evaluation %d: trial %.17g rejected, asks %.17g (x %.3g); shadows:",
-                                         p.theta, p.machine->evaluations(), stp[a], p.machine->trial_step(), p.machine->trial_step() / stp[a]);
-                            for (int q = 0; q < nshadow; ++q)
-                                if (shadow_owner[q] == a) std::fprintf(stderr, " x %.3g", shadow_stp[q] / stp[a]);
-                            std::fprintf(stderr, "\n");
-                        }
-                    }
                     // rejected: is the step it asks for next among this round's shadows?  An adopted evaluation may be
-                    // rejected in its turn: its successor may be there too (second-level shadows)
+                    // rejected in its turn: its successor may be there too (deeper shadows)
                     bool used[kMaxBatch] = {};
-                    double prev = 0.0;
+                    double prev = 0.0, tried = stp[a];
                     while (act.kind == LbfgsMachine::TRIAL) {
                         prev = p.machine->trial_step();
+                        p.prev_dir = p.last_dir;
+                        p.last_dir = prev < tried ? -1 : 1;
+                        tried = prev;
                         int q = 0;
                         for (; q < nshadow; ++q)
                             if (shadow_owner[q] == a && !used[q] && shadow_stp[q] == prev) break;
+                        if (dbg) ++dbg_rej[p.id];
                         if (q == nshadow) {
-                            if (dbg && column != a)
-                                std::fprintf(stderr, "spec debug: theta %g evaluation %d: adopted x %.3g rejected in its turn, asks x %.4g\n",
-                                             p.theta, p.machine->evaluations(), c->host_scal[0] * 0 + shadow_stp[column - k] / stp[a], prev / stp[a]);
+                            if (dbg) {         // a rejection that costs a round
+                                int mine = 0;
+                                for (int q2 = 0; q2 < nshadow; ++q2) mine += shadow_owner[q2] == a;
+                                if (!mine) ++dbg_noslot[p.id]; else ++dbg_miss[p.id];
+                                std::fprintf(stderr, "spec debug: theta %g round %d evaluation %d iteration %d: %s rejected, asks x %.4g of the round's step; "
+                                             "free slots %d, shadows:", p.theta, rounds, p.machine->evaluations(), p.machine->iterations(),
+                                             column == a ? "trial" : "adopted shadow", prev / stp[a], nfree0);
+                                for (int q2 = 0; q2 < nshadow; ++q2)
+                                    if (shadow_owner[q2] == a) std::fprintf(stderr, " x %.4g", shadow_stp[q2] / stp[a]);
+                                std::fprintf(stderr, "\n");
+                            }
                             break;
                         }
                         used[q] = true;
@@ -650,6 +678,7 @@ struct LogwBatchEngine {
                         act = p.machine->on_trial(t2);
                     }
                     if (act.kind == LbfgsMachine::ACCEPT) {
+                        p.last_dir = p.prev_dir = 0;
                         p.need_direction = true;
                         p.accept = true;
                         p.end = act.end;
@@ -672,8 +701,9 @@ struct LogwBatchEngine {
         c->spec_used += spec_used;
         if (dbg)
             for (int i = 0; i < ntheta; ++i)
-                std::fprintf(stderr, "spec debug: theta %g: %d rejected trials, %d without a shadow slot, %d with shadows but none matching\n",
-                             thetas[i], dbg_rej[i], dbg_noslot[i], dbg_miss[i]);
+                std::fprintf(stderr, "spec debug: theta %g: %d rejected trials, %d cost a round: %d without a shadow slot, %d with shadows but none matching\n",
+                             thetas[i], dbg_rej[i], dbg_noslot[i] + dbg_miss[i], dbg_noslot[i], dbg_miss[i]);
+        if (dbg) std::fprintf(stderr, "spec debug: %d rounds\n", rounds);
         if (verbose && spec_launched)
             std::printf("\tspeculative line-search evaluations: %lld issued in idle batch slots, %lld adopted\n",
                         spec_launched, spec_used);

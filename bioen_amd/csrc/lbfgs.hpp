@@ -64,6 +64,11 @@ class LbfgsMachine {
     double trial_step() const { return st_.stp; }
     // Steps the backtracking searches can ask for NEXT, should the pending trial be rejected (lbfgs_state.hpp)
     int speculative_steps(double out[2]) const { return lb::speculative_steps(st_.stp, cfg_.linesearch, out); }
+    // ... and the ones further rejections would lead to, most likely first (last_dir / prev_dir: the running search's last
+    // two moves as the caller has seen them; out: room for min(capacity, kLatticeMax) steps)
+    int speculative_lattice(int last_dir, int prev_dir, int capacity, double* out) const {
+        return lb::speculative_lattice(st_.stp, cfg_.linesearch, last_dir, prev_dir, st_.iterations, capacity, out);
+    }
     // Result of that evaluation.
     Action on_trial(const TrialResult& t) {
         st_.pf = pf_.data();          // machines live in containers: the storage may have moved with them

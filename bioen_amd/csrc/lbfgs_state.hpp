@@ -460,6 +460,69 @@ BIOEN_HD inline int speculative_steps(double stp, int linesearch, double out[2])
     return 2;
 }
 
+// The same, several rejections deep: the steps a backtracking search can ask for while the pending trial and its
+// successors are rejected, most likely first.  Every step is the pending one multiplied by 0.5 or 2.1 again and again in
+// the order the search would do it (the halving is exact: up-then-down and down-then-up are one number).
+//   1. both first-level steps, as speculative_steps: stp * 0.5, stp * 2.1
+//   2. the habit chain, kLatticeDepth moves deep: the move the search is expected to make next, then the one after ...
+//      -- a run of one move goes on, two different moves in a row alternate (last_dir / prev_dir: the running search's
+//      last two moves, -1 down, +1 up, 0 none yet).  A search without a move yet halves, except the first search of a
+//      problem (iteration 0): its start step 1 / |g| is a guess and is multiplied up
+//   3. what is left of the second level: stp * 0.25, stp * 4.41, stp * 1.05
+// Armijo searches (linesearch 1) only halve; More-Thuente steps cannot be foreseen (returns 0).  A step outside
+// [kMinStep, kMaxStep] is left out, and the chain ends there.  No step appears twice; at most `capacity` (and
+// kLatticeMax) are written.
+constexpr int kLatticeDepth = 6;
+constexpr int kLatticeMax = 9;    // 2 + (kLatticeDepth - 1) + 2
+
+BIOEN_HD inline void lattice_push(double v, double* out, int& n, int capacity) {
+    BIOEN_NO_CONTRACT
+    if (n >= capacity || !(kMinStep <= v && v <= kMaxStep)) return;
+    for (int i = 0; i < n; ++i)
+        if (out[i] == v) return;
+    out[n++] = v;
+}
+
+// the move a search makes next if it keeps its habit
+BIOEN_HD inline int lattice_next_move(int linesearch, int last_dir, int prev_dir, int iteration) {
+    if (linesearch == 1) return -1;
+    if (last_dir == 0) return iteration == 0 ? 1 : -1;
+    return (prev_dir != 0 && prev_dir != last_dir) ? -last_dir : last_dir;
+}
+
+BIOEN_HD inline int speculative_lattice(double stp, int linesearch, int last_dir, int prev_dir, int iteration, int capacity,
+                                        double* out) {
+    BIOEN_NO_CONTRACT
+    if (linesearch < 1 || linesearch > 3) return 0;
+    if (capacity > kLatticeMax) capacity = kLatticeMax;
+    int n = 0;
+    double dec = stp, inc = stp;
+    dec *= 0.5;
+    inc *= 2.1;
+    lattice_push(dec, out, n, capacity);
+    if (linesearch != 1) lattice_push(inc, out, n, capacity);
+    double v = stp;
+    int h1 = last_dir, h2 = prev_dir;
+    for (int depth = 0; depth < kLatticeDepth; ++depth) {
+        const int mv = lattice_next_move(linesearch, h1, h2, iteration);
+        v *= mv < 0 ? 0.5 : 2.1;
+        if (!(kMinStep <= v && v <= kMaxStep)) break;
+        lattice_push(v, out, n, capacity);
+        h2 = h1;
+        h1 = mv;
+    }
+    double dd = dec, ii = inc, di = inc;
+    dd *= 0.5;
+    ii *= 2.1;
+    di *= 0.5;
+    lattice_push(dd, out, n, capacity);
+    if (linesearch != 1) {
+        lattice_push(ii, out, n, capacity);
+        lattice_push(di, out, n, capacity);
+    }
+    return n;
+}
+
 }  // namespace lb
 
 }  // namespace bioen
