@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BIOEN_HIP_LIBRARY") or os.path.join(_HERE, "libbioen_hip.so")
 
 dp = C.POINTER(C.c_double)
+ip = C.POINTER(C.c_int)
 ctx_p = C.c_void_p
 
 
@@ -44,27 +45,27 @@ class OptResult(C.Structure):
 
 
 class NewtonConfig(C.Structure):
-    # bioen_newton_config (include/bioen_hip_forces_newton.h)
+    # bioen_newton_config (include/bioen_hip.h)
     _fields_ = [("gtol", C.c_double), ("armijo", C.c_double), ("rho_good", C.c_double), ("lambda_factor", C.c_double),
                 ("lambda_first", C.c_double), ("lambda_max", C.c_double), ("lambda_zero", C.c_double),
                 ("floor_ulps", C.c_double), ("max_iterations", C.c_int), ("hessian", C.c_int)]
 
 
 class NewtonResult(C.Structure):
-    # bioen_newton_result (include/bioen_hip_forces_newton.h)
+    # bioen_newton_result (include/bioen_hip.h)
     _fields_ = [("fmin", C.c_double), ("gmax", C.c_double), ("lam", C.c_double), ("status", C.c_int),
                 ("iterations", C.c_int), ("evaluations", C.c_int), ("hessians", C.c_int), ("factorisations", C.c_int),
                 ("switched", C.c_int)]
 
 
 class LogwNewtonConfig(C.Structure):
-    # bioen_logwn_config (include/bioen_hip_logw_newton.h)
+    # bioen_logwn_config (include/bioen_hip.h)
     _fields_ = [("gtol", C.c_double), ("armijo", C.c_double), ("floor_ulps", C.c_double), ("max_iterations", C.c_int),
                 ("max_halvings", C.c_int)]
 
 
 class LogwNewtonResult(C.Structure):
-    # bioen_logwn_result (include/bioen_hip_logw_newton.h)
+    # bioen_logwn_result (include/bioen_hip.h)
     _fields_ = [("fmin", C.c_double), ("gmax", C.c_double), ("wmax", C.c_double), ("status", C.c_int),
                 ("iterations", C.c_int), ("evaluations", C.c_int), ("factorisations", C.c_int)]
 
@@ -172,53 +173,23 @@ _SIGNATURES = {
     "bioen_hip_bfgs_logw_end": (C.c_int, [ctx_p, dp, dp, C.POINTER(OptResult)]),
     "bioen_hip_bfgs_logw_read_hinv": (C.c_int, [ctx_p, C.c_int, C.c_int, C.c_int, dp]),
     "bioen_hip_bfgs_logw_read_vec": (C.c_int, [ctx_p, C.c_int, dp]),
-}
-
-# every symbol include/bioen_hip_forces_hessp.h declares (the second public header: second-order information of the
-# forces method); bound by lib() beside the first table
-_SIGNATURES_FORCES_HESSP = {
+    # forces method: Hessian-vector products
     "bioen_hip_forces_hessp": (C.c_int, [ctx_p, dp, dp, C.c_double, C.c_int, dp, dp, dp, dp]),
-}
-
-# every symbol include/bioen_hip_forces_gram.h declares (the third public header: the dense Hessian and the covariance of
-# the forces method in one pass); bound by lib() beside the other two
-_SIGNATURES_FORCES_GRAM = {
+    # forces method: the dense Hessian and the covariance in one pass
     "bioen_hip_forces_gram": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp]),
-}
-
-# every symbol include/bioen_hip_forces_colquad.h declares (the fourth public header: one quadratic form per structure at
-# a kept forces point); bound by lib() beside the other three
-_SIGNATURES_FORCES_COLQUAD = {
+    # forces method: one quadratic form per structure at a kept forces point
     "bioen_hip_forces_colquad": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp]),
-}
-
-# every symbol include/bioen_hip_forces_gram_bf16.h declares (the fifth public header: the forces Hessian for a Newton
-# minimizer from split-BF16 operands); bound by lib() beside the other four
-_SIGNATURES_FORCES_GRAM_BF16 = {
+    # forces method: the Hessian for a Newton minimizer from split-BF16 operands
     "bioen_hip_forces_gram_bf16": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp]),
-}
-
-# every symbol include/bioen_hip_forces_newton.h declares (the sixth public header: the device-resident Newton minimizer
-# of the forces method, its Cholesky factorisation and solves); bound by lib() beside the other five
-_SIGNATURES_FORCES_NEWTON = {
+    # forces method: the device-resident Newton minimizer, its Cholesky factorisation and solves
     "bioen_hip_forces_newton_factor": (C.c_int, [ctx_p, dp, C.c_int, C.c_double, dp, C.POINTER(C.c_int)]),
     "bioen_hip_forces_newton_solve": (C.c_int, [ctx_p, C.c_int, dp, dp]),
     "bioen_hip_opt_newton_forces": (C.c_int, [ctx_p, dp, dp, C.c_double, C.POINTER(NewtonConfig), dp, dp,
                                               C.POINTER(NewtonResult)]),
-}
-
-# every symbol include/bioen_hip_forces_laplace.h declares (the seventh public header: the Laplace error bars of the forces
-# method without leaving the device; its entries are bioen_laplace_*, the bioen_hip_* names being closed over the six tables
-# above); bound by lib() beside the other six
-ip = C.POINTER(C.c_int)
-_SIGNATURES_FORCES_LAPLACE = {
+    # forces method: the Laplace error bars without leaving the device
     "bioen_laplace_forces_inverse": (C.c_int, [ctx_p, dp, dp, dp, ip]),
     "bioen_laplace_forces": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp, dp, dp, dp, dp, ip, dp, dp]),
-}
-
-# every symbol include/bioen_hip_logw_newton.h declares (the eighth public header: the log-weights method's dual Newton
-# minimizer and the covariance it is built on; its entries are bioen_logwn_*); bound by lib() beside the other seven
-_SIGNATURES_LOGW_NEWTON = {
+    # log-weights method: the dual Newton minimizer and the covariance it is built on
     "bioen_logwn_cov": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp]),
     "bioen_logwn_opt": (C.c_int, [ctx_p, dp, dp, C.c_double, C.POINTER(LogwNewtonConfig), dp, C.POINTER(LogwNewtonResult)]),
 }
@@ -228,34 +199,6 @@ _lib = None
 
 def exported_symbols():
     return sorted(_SIGNATURES)
-
-
-def exported_symbols_forces_hessp():
-    return sorted(_SIGNATURES_FORCES_HESSP)
-
-
-def exported_symbols_forces_gram():
-    return sorted(_SIGNATURES_FORCES_GRAM)
-
-
-def exported_symbols_forces_colquad():
-    return sorted(_SIGNATURES_FORCES_COLQUAD)
-
-
-def exported_symbols_forces_gram_bf16():
-    return sorted(_SIGNATURES_FORCES_GRAM_BF16)
-
-
-def exported_symbols_forces_newton():
-    return sorted(_SIGNATURES_FORCES_NEWTON)
-
-
-def exported_symbols_forces_laplace():
-    return sorted(_SIGNATURES_FORCES_LAPLACE)
-
-
-def exported_symbols_logw_newton():
-    return sorted(_SIGNATURES_LOGW_NEWTON)
 
 
 def lib():
@@ -268,13 +211,10 @@ def lib():
                 "(or `python -c 'import __graft_entry__ as e; e.build()'`). "
                 "There is no CPU fallback." % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _SIGNATURES_FORCES_HESSP, _SIGNATURES_FORCES_GRAM, _SIGNATURES_FORCES_COLQUAD,
-                      _SIGNATURES_FORCES_GRAM_BF16, _SIGNATURES_FORCES_NEWTON, _SIGNATURES_FORCES_LAPLACE,
-                      _SIGNATURES_LOGW_NEWTON):
-            for name, (res, args) in table.items():
-                fn = getattr(L, name)          # AttributeError here = header/library mismatch
-                fn.restype = res
-                fn.argtypes = args
+        for name, (res, args) in _SIGNATURES.items():
+            fn = getattr(L, name)          # AttributeError here = header/library mismatch
+            fn.restype = res
+            fn.argtypes = args
         _lib = L
     return _lib
 

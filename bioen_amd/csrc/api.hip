@@ -18,12 +18,6 @@
 
 #include "ctx.hpp"
 #include "host.hpp"
-#include "../../include/bioen_hip_forces_hessp.h"
-#include "../../include/bioen_hip_forces_gram.h"
-#include "../../include/bioen_hip_forces_colquad.h"
-#include "../../include/bioen_hip_forces_gram_bf16.h"
-#include "../../include/bioen_hip_forces_newton.h"
-#include "../../include/bioen_hip_forces_laplace.h"
 #include "kernels.hpp"
 #include "lbfgs.hpp"
 #include "multimin.hpp"

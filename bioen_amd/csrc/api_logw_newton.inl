@@ -5,8 +5,6 @@
 // loop is log_weights.py's dual_newton_bioen_log_posterior_base, decision for decision.  The point is bioen_hip_logw_hessp's:
 // set, kept and refused by api_forces_point.inl's logw_point_prologue / logw_keep_point, the entries guarded by its dense_guard.
 
-#include "../../include/bioen_hip_logw_newton.h"
-
 namespace bioen {
 
 static const PointWords kLogwnPoint = {"call with g", "set a log-weights point first (bioen_logwn_cov or bioen_hip_logw_hessp with g)"};

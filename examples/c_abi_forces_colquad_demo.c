@@ -1,4 +1,4 @@
-/* A C99 caller of include/bioen_hip_forces_colquad.h: a small forces problem, the point set with the spread of every
+/* A C99 caller of include/bioen_hip.h: a small forces problem, the point set with the spread of every
  * structure (P = I) in one call, the result checked against |a_j|^2 formed here from the weights, the call at the kept
  * point for the same bits, an unsymmetric P rejected, a call refused after another evaluation.  Leaves with 0 and "ok",
  * with 77 where there is no HIP device (there is no CPU path), with 1 on a failure. */
@@ -7,7 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "bioen_hip_forces_colquad.h"
+#include "bioen_hip.h"
 
 #define M 24
 #define N 300

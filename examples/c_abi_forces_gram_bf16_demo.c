@@ -1,4 +1,4 @@
-/* A C99 caller of include/bioen_hip_forces_gram_bf16.h: a small forces problem, the point set with the split-BF16
+/* A C99 caller of include/bioen_hip.h: a small forces problem, the point set with the split-BF16
  * covariance and Hessian in one call, both checked for exact symmetry and against bioen_hip_forces_gram's FP64 results at
  * the same kept point (1e-3 of the largest entry: what a minimizer's Hessian may be off by), the call at the kept point
  * for the same bits, a call refused after another evaluation.  Leaves with 0 and "ok", with 77 where there is no HIP
@@ -8,8 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "bioen_hip_forces_gram.h"
-#include "bioen_hip_forces_gram_bf16.h"
+#include "bioen_hip.h"
 
 #define M 24
 #define N 300

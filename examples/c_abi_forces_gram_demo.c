@@ -1,4 +1,4 @@
-/* A C99 caller of include/bioen_hip_forces_gram.h: a small forces problem, the point set with the covariance and the
+/* A C99 caller of include/bioen_hip.h: a small forces problem, the point set with the covariance and the
  * Hessian in one call, both checked for exact symmetry, the covariance for a non-negative diagonal, the call at the kept
  * point for the same bits, a call refused after another evaluation.  Leaves with 0 and "ok", with 77 where there is no
  * HIP device (there is no CPU path), with 1 on a failure. */
@@ -6,7 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "bioen_hip_forces_gram.h"
+#include "bioen_hip.h"
 
 #define M 24
 #define N 300

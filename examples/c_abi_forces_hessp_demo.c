@@ -1,11 +1,11 @@
-/* A C99 caller of include/bioen_hip_forces_hessp.h: a small forces problem, the point set, two products at it checked
+/* A C99 caller of include/bioen_hip.h: a small forces problem, the point set, two products at it checked
  * for symmetry (v1 . H v0 = v0 . H v1), a product refused after another evaluation.  Leaves with 0 and "ok", with 77
  * where there is no HIP device (there is no CPU path), with 1 on a failure. */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "bioen_hip_forces_hessp.h"
+#include "bioen_hip.h"
 
 #define M 24
 #define N 300

@@ -1,4 +1,4 @@
-/* A C99 caller of include/bioen_hip_forces_laplace.h: a caller's matrix inverted on the device from its Cholesky factor (A
+/* A C99 caller of include/bioen_hip.h: a caller's matrix inverted on the device from its Cholesky factor (A
  * Ainv = I and the symmetry checked), a pivot failure reported as LAPACK's info with nothing written, then a small forces
  * problem minimised by the device-resident Newton loop and the Laplace error bars taken at the optimum, which the loop
  * leaves as the kept point: only the M + N numbers of the error bars come down.  Leaves with 0 and "ok", with 77 where
@@ -8,8 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "bioen_hip_forces_laplace.h"
-#include "bioen_hip_forces_newton.h"
+#include "bioen_hip.h"
 
 #define M 24
 #define N 300

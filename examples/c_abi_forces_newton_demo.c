@@ -1,4 +1,4 @@
-/* A C99 caller of include/bioen_hip_forces_newton.h: a caller's matrix factorised and solved on the device (the residual
+/* A C99 caller of include/bioen_hip.h: a caller's matrix factorised and solved on the device (the residual
  * checked), a pivot failure reported as LAPACK's info and the solve behind it refused, then a small forces problem
  * minimised by the device-resident Newton loop and the Hessian of the optimum, which the loop leaves as the kept point,
  * factorised in place.  Leaves with 0 and "ok", with 77 where there is no HIP device (there is no CPU path), with 1 on a
@@ -8,8 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "bioen_hip_forces_gram.h"
-#include "bioen_hip_forces_newton.h"
+#include "bioen_hip.h"
 
 #define M 24
 #define N 300

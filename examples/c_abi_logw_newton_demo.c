@@ -1,4 +1,4 @@
-/* A C99 caller of include/bioen_hip_logw_newton.h: a small log-weights problem minimised by the device-resident dual Newton
+/* A C99 caller of include/bioen_hip.h: a small log-weights problem minimised by the device-resident dual Newton
  * loop, then the covariance of the observables under the refined weights, served at the point the loop leaves and again by
  * an evaluation of the returned log-weights (the same bits), with its trace checked against the weighted variances.
  * Leaves with 0 and "ok", with 77 where there is no HIP device (there is no CPU path), with 1 on a failure. */
@@ -7,7 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "bioen_hip_logw_newton.h"
+#include "bioen_hip.h"
 
 #define M 24
 #define N 300

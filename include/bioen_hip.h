@@ -171,8 +171,8 @@ int bioen_hip_ctx_read_ytilde(bioen_hip_ctx* ctx, int row0, int rows, int col0, 
  * be allocated -- the adjoint then runs on the row-sum order copy (1-3 % slower per launch, same minima, last bits differ
  * from the two-copy default: the sums over rows are formed in another order). */
 /* (bit 3: copies of the reduced-storage experiment, bioen_hip_ctx_set_storage, beside the FP64 row-major matrix) */
-/* (bit 5: the device buffer of bioen_hip_forces_gram, bioen_hip_forces_gram.h, from its first call on) */
-/* (bit 6: the device buffer of bioen_hip_forces_colquad, bioen_hip_forces_colquad.h, from its first call on) */
+/* (bit 5: the device buffer of bioen_hip_forces_gram, from its first call on) */
+/* (bit 6: the device buffer of bioen_hip_forces_colquad, from its first call on) */
 int bioen_hip_ctx_footprint(const bioen_hip_ctx* ctx, int* forms, long long* bytes);
 /* r06: HOW the strip copies are held.  one_copy: 1 = the log-weights adjoint runs on the row-sum order copy (asked for, or
  * taken by THIS rank because the second copy could not be allocated -- its last bits then differ from a two-copy rank's:
@@ -494,6 +494,250 @@ int bioen_hip_exchange_counts3(const bioen_hip_ctx* ctx, long long* rccl, long l
  * is gone; an RCCL communicator is aborted with ncclCommAbort so that its kernel returns) or BIOEN_HIP_EHIP, with
  * bioen_hip_last_error() naming what was awaited.  The context is unusable afterwards (BIOEN_HIP_ESTATE): destroy it. */
 int bioen_hip_ctx_set_wait_timeout(bioen_hip_ctx* ctx, double seconds);
+
+/* ---- forces method: Hessian-vector products ------------------------------------------------------------------------ */
+/* H(forces) v for k <= 8 directions of the forces objective L(f) = theta KL(w || w0) + 0.5 |ybar - YTilde|^2 (of the
+ * affine model if bioen_hip_ctx_set_affine has set one); v, hv: k x m, row-major.  H is the exact Hessian: symmetric,
+ * not positive definite away from the optimum.  No reference counterpart (the reference has first-order drivers only).
+ *
+ * forces != NULL (with w0): evaluates the point first -- bioen_hip_forces_fdf with a gradient, launch for launch: f and
+ * grad (optional outputs) are its bits -- and keeps it on the context, at the cost of one column-sum pass more;
+ * k == 0 then only sets the point.  forces == NULL: a product at the point kept by the last such call (w0, theta
+ * ignored): two fused matrix passes, what a gradient costs, whatever k.
+ *
+ * A context keeps ONE point, of either method: this entry and bioen_hip_logw_hessp replace each other's, every call that
+ * evaluates, optimises or changes the matrix state drops it (BIOEN_HIP_ESTATE from the next product, naming the call),
+ * and a product on a point of the other method is BIOEN_HIP_ESTATE.  A call rejected for its arguments (BIOEN_HIP_EINVAL)
+ * or refused for the context's state leaves point, BFGS session and device alone.
+ *
+ * Served: the FP64 strip copies, on any number of ranks (k directions in one call give the bits of k calls, one GPU the
+ * bits of 2, 4 or 8) -- M <= 1024: two fused passes per product; M > 1024: two column-sum and two row-sum passes per row
+ * panel, as the evaluation there, and setting the point costs no pass more.  Refused with BIOEN_HIP_ESTATE: contexts
+ * without the strip copies (the streaming fallback), the reduced-storage experiment's copies.
+ * bioen_hip_kernel_stats: which = 6 / 7 are the two fused passes of a product (M <= 1024). */
+int bioen_hip_forces_hessp(bioen_hip_ctx* ctx, const double* forces, const double* w0, double theta, int k,
+                           const double* v, double* hv, double* f, double* grad);
+
+/* ---- forces method: the dense Hessian and the covariance of the observables in one pass over the matrix ------------ */
+/* cov = C, the covariance of the observables under the weights of the point (= d ybar / d forces), and hess = H, the
+ * exact Hessian of L(f) = theta KL(w || w0) + 0.5 |ybar - YTilde|^2 at it (of the affine model if
+ * bioen_hip_ctx_set_affine has set one); both m x m, row-major, bitwise symmetric; either may be NULL.  With
+ * a_j = A_:j - ybar and q_j = theta x_j + b_j:  C = sum_j w_j a_j a_j^T,  H = theta C + C C + sum_j w_j (q_j - qbar) a_j a_j^T
+ * -- ONE compute-bound pass over the matrix on the FP64 matrix cores for both, where bioen_hip_forces_hessp needs
+ * 2 ceil(m / 8) bandwidth-bound ones for H.  No reference counterpart.
+ *
+ * The point is bioen_hip_forces_hessp's.  forces != NULL (with w0): evaluates the point first -- bioen_hip_forces_fdf
+ * with a gradient, launch for launch: f and grad (optional outputs) are its bits --, keeps it on the context and ends
+ * a BFGS session.  forces == NULL: serves the kept forces point (w0, theta ignored), keeps point and session; refused
+ * with BIOEN_HIP_ESTATE on a log-weights point or without a point.  A call rejected for its arguments
+ * (BIOEN_HIP_EINVAL: forces without w0; nothing asked for) or refused for the context's state leaves point, session
+ * and device alone.
+ *
+ * Two calls at one point give the same bits (fixed summation order, no atomics); a call that sets the point gives the
+ * bits of a call that serves it.  Refused with BIOEN_HIP_ESTATE: m > 1024 (row panels), contexts without the strip
+ * copies, the reduced-storage experiment's copies, structure-sharded contexts.  The device buffer of the partial
+ * sums is allocated at the first call and freed with the context (bioen_hip_ctx_footprint: bit 5).  Its size is
+ * O(sets x m^2) whatever n is -- sets = 8 segments x ceil(512 / (8 tiles)) groups, each holding the lower triangle's 64 x 64
+ * sub-tiles of both matrices: 117 MB at m = 256, 139 MB at m = 512, 168 MB at m = 1024, 4 MB at m = 7 -- so a small
+ * matrix does not make it small: callers that keep many small contexts should use bioen_hip_forces_hessp there. */
+int bioen_hip_forces_gram(bioen_hip_ctx* ctx, const double* forces, const double* w0, double theta,
+                          double* cov, double* hess, double* f, double* grad);
+
+/* ---- forces method: one quadratic form per structure at a kept forces point, in one pass over the matrix ----------- */
+/* out_j = a_j^T P a_j, j = 0 .. n - 1, with a_j = A_:j - ybar the j-th structure's observables (of the affine model if
+ * bioen_hip_ctx_set_affine has set one: a_j = S (Y_:j - ybar), S = diag(scale)) centred on the averages under the
+ * weights of the point, and P a symmetric m x m matrix, row-major.  Because d ln w_j / d forces = a_j:
+ *   P = H^-1 (bioen_hip_forces_gram's H)  the Laplace variance of ln w_j around an optimum,
+ *   P = C^-1                              the structure's Mahalanobis distance from the refined ensemble,
+ *   P = I                                 its spread |a_j|^2.
+ * ONE compute-bound pass over the matrix on the FP64 matrix cores (2 m^2 n flops), where the column sums of
+ * bioen_hip_forces_hessp's passes would need ceil(m / 8) bandwidth-bound ones.  No reference counterpart.
+ *
+ * The point is bioen_hip_forces_hessp's, with bioen_hip_forces_gram's semantics.  forces != NULL (with w0): evaluates
+ * the point first -- bioen_hip_forces_fdf with a gradient, launch for launch: f and grad (optional outputs) are its
+ * bits --, keeps it on the context and ends a BFGS session; P == NULL then only sets the point (out is not written).
+ * forces == NULL: serves the kept forces point (w0, theta ignored), keeps point and session; refused with
+ * BIOEN_HIP_ESTATE on a log-weights point or without a point.  A call rejected for its arguments (BIOEN_HIP_EINVAL:
+ * forces without w0; neither forces nor P; P without out; "P is not symmetric": |P_ij - P_ji| > 1e-12 max |P|) or
+ * refused for the context's state leaves point, session and device alone.  Non-finite entries of P are the caller's
+ * business.  What is computed is the form of the symmetric part (P + P^T) / 2.
+ *
+ * Two calls at one point give the same bits (every out_j has one writer, fixed summation order, no atomics).  Refused
+ * with BIOEN_HIP_ESTATE: m > 1024 (row panels), contexts without the strip copies, the reduced-storage experiment's
+ * copies, structure-sharded contexts.  The device buffer -- P padded to a multiple of 16 rows, and the n results -- is
+ * allocated at the first call that computes and freed with the context (bioen_hip_ctx_footprint: bit 6). */
+int bioen_hip_forces_colquad(bioen_hip_ctx* ctx, const double* forces, const double* w0, double theta,
+                             const double* P, double* out, double* f, double* grad);
+
+/* ---- forces method: the dense Hessian for a Newton minimizer, from split-BF16 operands on the BF16 matrix cores ---- */
+/* cov = C~ and hess = H~: bioen_hip_forces_gram's C and H (above: the same formulas, arguments, layout
+ * and point semantics) with the two M x M x N products formed from split-BF16 operands -- every operand is hi + lo, two
+ * bfloat16 numbers, the products hi hi + hi lo + lo hi are accumulated in f32 -- at 32 x the matrix rate of FP64.
+ * Everything else (the point, its weights, the row sums, the rank corrections, theta C + G2 + C C) stays FP64.  The
+ * result is a MINIMIZER's Hessian, good to about 1e-5 .. 1e-4 of max|H|: it shapes a Newton step, whose gradient (f and
+ * grad of this entry are bioen_hip_forces_fdf's bits) decides the optimum.  Error bars and anything else that needs C
+ * or H themselves take them from bioen_hip_forces_gram, which this entry leaves bitwise alone.
+ *
+ * Both matrices are m x m, row-major, bitwise symmetric; either may be NULL.  forces != NULL (with w0): evaluates the
+ * point first, keeps it on the context and ends a BFGS session.  forces == NULL: serves the kept forces point (w0,
+ * theta ignored), keeps point and session; refused with BIOEN_HIP_ESTATE on a log-weights point or without a point.  A
+ * call rejected for its arguments (BIOEN_HIP_EINVAL: forces without w0; nothing asked for) or refused for the
+ * context's state leaves point, session and device alone.
+ *
+ * Two calls at one point give the same bits (fixed summation order, no atomics; the sets' f32 sums are added in FP64).
+ * Refused with BIOEN_HIP_ESTATE: m > 1024 (row panels), contexts without the strip copies, the reduced-storage
+ * experiment's copies, structure-sharded contexts.  The device buffer of the partial sums is this entry's own, of
+ * bioen_hip_forces_gram's size, allocated at the first computing call and freed with the context
+ * (bioen_hip_ctx_footprint: bit 7). */
+int bioen_hip_forces_gram_bf16(bioen_hip_ctx* ctx, const double* forces, const double* w0, double theta,
+                               double* cov, double* hess, double* f, double* grad);
+
+/* ---- forces method: device-resident Newton minimizer -- the dense Hessian stays in device memory, is factorised
+ *      (FP64 Cholesky) and solved there, and the loop runs behind one call.
+ *
+ * All three entries are refused with BIOEN_HIP_ESTATE, each case with a message of its own, where
+ * bioen_hip_forces_gram_bf16 is: m > 1024 (row panels), contexts without the strip copies, the reduced-storage
+ * experiment's copies, structure-sharded contexts. ---- */
+
+/* A + lambda I = L L^T, L lower triangular, on the device (blocked, right-looking, panels of 64; the trailing update on
+ * the FP64 matrix cores).  Only the lower triangle of the matrix is read.
+ *   A != NULL: an m x m row-major host matrix (source is ignored).
+ *   A == NULL: the Hessian of the kept forces point, computed now on the device and not downloaded -- source 0:
+ *              bioen_hip_forces_gram's H, source 1: bioen_hip_forces_gram_bf16's.  Refused with BIOEN_HIP_ESTATE without
+ *              a forces point.
+ * *info (required) is LAPACK dpotrf's: 0 and L is complete, or k + 1 where pivot k was <= 0 or not finite -- an ordinary
+ * result (the call returns 0), after which no kernel of the factorisation has touched the rest of the matrix.  L (may be
+ * NULL): m x m row-major, zeros above the diagonal; written only when *info == 0.  The order of every sum is a function
+ * of m alone: the same bits in give the same bits out.  Keeps point and session.  The device buffer of L is this
+ * section's own, allocated at the first call and freed with the context (bioen_hip_ctx_footprint: bit 8). */
+int bioen_hip_forces_newton_factor(bioen_hip_ctx* ctx, const double* A, int source, double lambda, double* L, int* info);
+
+/* X = (L L^T)^-1 B with the factor of the last bioen_hip_forces_newton_factor call; B, X: [k][m], 1 <= k <= 8 (they may
+ * be the same buffer).  A right-hand side's result does not depend on k.  BIOEN_HIP_ESTATE if there is no factor, or if
+ * the last factorisation ended with info != 0.  Keeps point and session. */
+int bioen_hip_forces_newton_solve(bioen_hip_ctx* ctx, int k, const double* B, double* X);
+
+typedef struct {
+    double gtol;            /* ends with status 0 when max |g_i| <= gtol */
+    double armijo;          /* a step is accepted when f+ - f <= -armijo * pred                          (1e-4) */
+    double rho_good;        /* lambda shrinks after a step with (f - f+) / pred above this               (0.75) */
+    double lambda_factor;   /* lambda grows and shrinks by this factor                                   (4)    */
+    double lambda_first;    /* the first lambda > 0, in units of d = max |diag H|                        (1e-10) */
+    double lambda_max;      /* status 3 when lambda exceeds this many d                                  (1e10) */
+    double lambda_zero;     /* a lambda below this many d becomes 0                                      (1e-12) */
+    double floor_ulps;      /* pred <= floor_ulps * epsilon * |f|: f cannot judge the step, max |g| does  (8)    */
+    int max_iterations;     /* accepted steps; status 1 when reached */
+    int hessian;            /* 0: bioen_hip_forces_gram's H, 1: bioen_hip_forces_gram_bf16's */
+} bioen_newton_config;
+
+typedef struct {
+    double fmin;            /* objective at the returned forces */
+    double gmax;            /* max |g_i| there */
+    double lambda;          /* the final damping */
+    int status;             /* 0: max|g| <= gtol; 1: max_iterations; 2: at the minimum to the rounding of f (a step at the
+                               rounding floor did not lower max|g|); 3: lambda grew beyond lambda_max * d */
+    int iterations;         /* accepted steps */
+    int evaluations;        /* evaluations of f and g (each two matrix passes and the point's one) */
+    int hessians;           /* Hessian passes */
+    int factorisations;
+    int switched;           /* 1: the run began with hessian = 1 and went over to 0 at the rounding floor */
+} bioen_newton_result;
+
+/* Regularised Newton on the forces objective from forces0 [m] (DESIGN 6h has the loop; forces.py's
+ * newton_bioen_log_posterior_base restates it in numpy, decision for decision): H at the kept point from `hessian`,
+ * H + lambda I factorised and solved on the device -- only m doubles go down and m come up per step --, the trial
+ * evaluated as bioen_hip_forces_hessp evaluates a point, so that an accepted trial is the kept point of the next Hessian.
+ * forces_out [m] (required), weights_out [n] (may be NULL), result (required).  Returns 0 with every status; the
+ * returned point is then the context's kept point (bioen_hip_forces_gram and bioen_hip_forces_colquad serve it at once).
+ * Ends a BFGS session. */
+int bioen_hip_opt_newton_forces(bioen_hip_ctx* ctx, const double* forces0, const double* w0, double theta,
+                                const bioen_newton_config* config, double* forces_out, double* weights_out,
+                                bioen_newton_result* result);
+
+/* ---- forces method: Laplace error bars without leaving the device -- the dense Hessian
+ * of bioen_hip_forces_gram is factorised where it stands (the kernels of bioen_hip_forces_newton_factor), inverted from
+ * the factor, and the inverse is handed to the quadratic-form pass of bioen_hip_forces_colquad in device memory.  Only
+ * what the caller asks for is downloaded: O(M + N) doubles per point for the error bars themselves.
+ *
+ * With H = L L^T and W = L^-1:
+ *   cov_forces   = H^-1     = W^T W
+ *   cov_averages = C H^-1 C = B^T B,  B = W C
+ *   var_logw_j   = a_j^T H^-1 a_j
+ *   logdet       = 2 sum_i ln L_ii
+ * Both covariances are bitwise symmetric, and the same bits in give the same bits out.
+ *
+ * Both entries are refused with BIOEN_HIP_ESTATE, each case with a message of its own, where bioen_hip_forces_gram is:
+ * m > 1024 (row panels), contexts without the strip copies, the reduced-storage experiment's copies, structure-sharded
+ * contexts.  A rejected call leaves point, session and device alone.  The device buffers (W, H^-1, B, C H^-1 C) are this
+ * section's own, allocated at the first call and freed with the context (bioen_hip_ctx_footprint: bit 9, value 512). ---- */
+
+/* H^-1 of a caller's symmetric positive definite m x m row-major matrix A (only the lower triangle is read), or with
+ * A == NULL of the Hessian (bioen_hip_forces_gram's, FP64) of the kept forces point (BIOEN_HIP_ESTATE without one).  The
+ * factor becomes the context's factor: bioen_hip_forces_newton_solve afterwards solves with it.  Ainv (m x m) and logdet
+ * may be NULL: the inverse stays resident.  *info (required) as LAPACK's dpotrf: 0, or k + 1 where pivot k was <= 0 or
+ * not finite -- an ordinary result (the call returns 0) after which nothing is written, neither Ainv nor logdet nor the
+ * resident inverse.  Keeps point and session. */
+int bioen_laplace_forces_inverse(bioen_hip_ctx* ctx, const double* A, double* Ainv, double* logdet, int* info);
+
+/* The error bars at a forces point.  With forces [m] (and w0 [n], theta) the point is evaluated and kept, as by
+ * bioen_hip_forces_gram with forces: *f and grad [m] (either may be NULL) are bioen_hip_forces_fdf's bits, and a BFGS
+ * session ends.  With forces == NULL the kept forces point is served (BIOEN_HIP_ESTATE without one; point and session
+ * stay).  Every output may be NULL, and only what is asked for is computed and downloaded:
+ *   std_forces [m], std_averages [m]      the roots of the covariances' diagonals (averages in the units of yTilde)
+ *   var_logw [n]                          the Laplace variance of every ln w_j
+ *   cov_forces, cov_averages [m x m]      row-major
+ *   *logdet                               ln det H
+ *   *min_pivot                            min_i L_ii^2: the caller judges definiteness against the scale of H
+ * *info (required) as LAPACK's dpotrf; with *info != 0 the call returns 0 and writes nothing else (f and grad apart). */
+int bioen_laplace_forces(bioen_hip_ctx* ctx, const double* forces, const double* w0, double theta, double* std_forces,
+                         double* std_averages, double* var_logw, double* cov_forces, double* cov_averages, double* logdet,
+                         double* min_pivot, int* info, double* f, double* grad);
+
+/* ---- log-weights method: dual Newton minimizer -- the N log-weights through an M x M system that
+ * is formed, factorised (FP64 Cholesky) and solved in device memory, and the covariance of the observables under the
+ * refined weights it is built on.  DESIGN section 6j.
+ *
+ * Both entries are refused with BIOEN_HIP_ESTATE, each case with a message of its own, on m > 1024 (row panels), on contexts
+ * without the strip copies, on the reduced-storage experiment's copies and on structure-sharded contexts. ---- */
+
+/* C = sum_j w_j (y_j - ybar)(y_j - ybar)^T, w = softmax(g): the covariance of the (affine model: effective) observables
+ * under the weights of a log-weights point, m x m row-major, bitwise symmetric; the same bits call after call.
+ *   g != NULL: an evaluation (bioen_hip_logw_hessp's with k = 0: the same f and grad, both optional) that leaves g as the
+ *              context's kept log-weights point; G [n] is required then.  C may be NULL: the call only sets the point.
+ *   g == NULL: serves the kept log-weights point (set by this entry, by bioen_hip_logw_hessp or by bioen_logwn_opt);
+ *              BIOEN_HIP_ESTATE without one, naming what dropped it.  G, theta, f and grad are ignored.
+ * The device buffer of the pass is this section's own, allocated at the first call that computes C and freed with the
+ * context (bioen_hip_ctx_footprint: bit 10). */
+int bioen_logwn_cov(bioen_hip_ctx* ctx, const double* g, const double* G, double theta, double* C, double* f, double* grad);
+
+typedef struct {
+    double gtol;            /* ends with status 0 when max |grad_k| <= gtol * max w_k (and max |gamma_k| <= theta) */
+    double armijo;          /* a step alpha u is accepted when f+ - f <= armijo * alpha * grad . u                (1e-4) */
+    double floor_ulps;      /* |alpha grad . u| <= floor_ulps * epsilon * |f|: f cannot judge the step, max |grad| does (8) */
+    int max_iterations;     /* accepted steps; status 1 when reached */
+    int max_halvings;       /* trials of one step, alpha = 1, 1/2, ...; status 3 when exhausted                   (60) */
+} bioen_logwn_config;
+
+typedef struct {
+    double fmin;            /* objective at the returned log-weights */
+    double gmax;            /* max |grad_k| there */
+    double wmax;            /* max w_k there */
+    int status;             /* 0: the gradient test; 1: max_iterations; 2: a step at the rounding floor of f did not lower
+                               max |grad|; 3: the step was exhausted elsewhere (or C + theta I did not factorise) */
+    int iterations;         /* accepted steps */
+    int evaluations;        /* evaluations of f and grad (status 2, 3: one more than the trials, to restore the point) */
+    int factorisations;
+} bioen_logwn_result;
+
+/* The dual Newton minimizer of the log-weights objective from g0 [n] with the prior G [n] (DESIGN 6j has the loop;
+ * log_weights.py's dual_newton_bioen_log_posterior_base restates it in numpy, decision for decision): per iteration one
+ * covariance pass, one factorisation of C + theta I and one solve on the device, one centred adjoint pass, and one
+ * evaluation per trial; every N-vector stays in device memory.  theta > 0 is required (BIOEN_HIP_EINVAL otherwise: the step
+ * divides by theta).  gopt [n] (required) is in the gauge the steps leave it in: compare weights, not g.  Returns 0 with
+ * every status; the returned point is then the context's kept log-weights point (bioen_logwn_cov and bioen_hip_logw_hessp
+ * without g serve it at once).  Ends a BFGS session. */
+int bioen_logwn_opt(bioen_hip_ctx* ctx, const double* g0, const double* G, double theta, const bioen_logwn_config* config,
+                    double* gopt, bioen_logwn_result* result);
 
 #ifdef __cplusplus
 }

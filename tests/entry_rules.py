@@ -1,17 +1,50 @@
-"""The rules every public header beside include/bioen_hip.h is held to -- those tests/test_abi.py and
-tests/test_entry_effects.py hold that one to: what it declares is exported and bound in its own table of _lib.py, it is
-plain C and a C caller links against it, and every entry has an effect row that is exercised on the GPU.
-Not a test module: tests/test_abi_forces_*.py each describe their header with a HeaderRules, call these checks from test
-functions of their own (so every file keeps its test ids) and add what they check beyond them."""
+"""What the tests of the C ABI's entries share: the effect row, the problem the rows run on, and the
+checks tests/test_abi_<feature>.py hold a feature's entries to -- every entry has its effect rows, a C caller compiles
+against include/bioen_hip.h as strict C99, links and runs, and every row is exercised on the GPU.  Not a test module:
+tests/test_entry_effects.py reads the rows of every tests/test_abi_*.py, and those describe their entries with an
+EntryRules and call its checks from test functions of their own (so every file keeps its test ids)."""
 import os
 import re
 import subprocess
+from collections import namedtuple
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from test_entry_effects import ALPHA, BETA, P, estate
+from conftest import ROOT, load_golden
+
+# point:   keeps | drops | sets (leaves a new one) | needs (fails without one, keeps it)
+# session: keeps | ends | needs (fails without one, keeps it; closes=True: its regular end) | starts
+# how:     the call on a bioen_amd.Context (the raw binding where it has no method); None + why: not runnable in one process on one GPU
+# prepare: what a live session (or the context) needs before the call can succeed
+Row = namedtuple("Row", "point session how prepare closes why", defaults=(None, False, None))
+
+ALPHA, BETA = 1e-3, 2e-3           # the trial the session is left at; another one
+
+
+class P(object):
+    """the problem of the tests: synth_logw_M64xN2000 (state logic: the shape does not matter)"""
+    _d = None
+
+    @classmethod
+    def get(cls):
+        if cls._d is None:
+            d = load_golden("synth_logw_M64xN2000.npz")
+            p = cls._d = cls()
+            p.yT, p.YT = d["yTilde"], d["YTilde"].reshape(-1)
+            p.G, p.theta, p.x = d["G"].reshape(-1), float(d["theta"]), d["GInit"].reshape(-1)
+            p.m, p.n = p.yT.shape
+            p.v = np.random.default_rng(1).standard_normal(p.n)
+            p.w0 = np.full(p.n, 1.0 / p.n)
+            p.f0 = np.zeros(p.m)
+        return cls._d
+
+
+def estate(call, *needles):
+    from bioen_amd._lib import BioenHipError
+    with pytest.raises(BioenHipError) as e:
+        call()
+    assert "(-6)" in str(e.value) and all(s in str(e.value) for s in needles), str(e.value)
 
 
 def v():
@@ -29,42 +62,29 @@ def bioen_amd():
     return bioen_amd
 
 
-class HeaderRules(object):
-    """header: the file under include/; names: what it declares, sorted; table: the suffix of _lib.py's
-    exported_symbols_<table>() and _SIGNATURES_<TABLE>; demo: the C caller under examples/, without .c; entries: name ->
-    [Row]; points: the values a row's point may take"""
+def short_name(name):
+    """an entry without its namespace -- bioen_ and the word after it: bioen_hip_, bioen_laplace_, bioen_logwn_ --: what
+    the ids of the effect tests are made of"""
+    return re.sub(r"^bioen_[a-z0-9]+_", "", name)
 
-    def __init__(self, header, names, table, demo, entries, points=("sets", "needs")):
-        self.header = os.path.join(ROOT, "include", header)
-        self.names, self.table, self.demo, self.entries, self.points = names, table, demo, entries, points
 
-    def declared_functions(self):
-        src = re.sub(r"/\*.*?\*/", "", open(self.header).read(), flags=re.S)
-        return sorted(set(re.findall(r"\b(bioen_hip_\w+)\s*\(", src)))
+class EntryRules(object):
+    """names: a feature's entries, sorted; demo: its C caller under examples/, without .c; entries: name -> [Row];
+    points: the values a row's point may take"""
+
+    def __init__(self, names, demo, entries, points=("sets", "needs")):
+        self.names, self.demo, self.entries, self.points = names, demo, entries, points
 
     def rows(self):
-        """the parameters of the effect tests: <entry without bioen_hip_>-<index of the row>"""
-        return [pytest.param(row, id="%s-%d" % (name[len("bioen_hip_"):], i))
-                for name in self.names for i, row in enumerate(self.entries[name])]
+        """the parameters of the effect tests: <entry without its prefix>-<index of the row>"""
+        return [pytest.param(row, id="%s-%d" % (short_name(name), i))
+                for name in sorted(self.entries) for i, row in enumerate(self.entries[name])]
 
-    def check_declared_exported_bound_and_classified(self):
-        """-> (names, every symbol the library exports), for what a file checks about the other tables"""
-        from bioen_amd import _lib
-        names = self.declared_functions()
-        assert names == self.names
-        out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-        exported = set(line.split()[-1] for line in out.splitlines() if line.strip())
-        assert not [n for n in names if n not in exported]
-        assert sorted(getattr(_lib, "exported_symbols_" + self.table)()) == names      # bound in its table, nothing else there
-        assert not set(names) & set(_lib.exported_symbols())                           # ... and the first table is bioen_hip.h's alone
-        L = _lib.lib()
-        for n in names:
-            assert getattr(L, n).argtypes == getattr(_lib, "_SIGNATURES_" + self.table.upper())[n][1]
-        assert set(self.entries) == set(names)                                         # every entry has its effect rows
+    def check_classified(self):
+        assert set(self.entries) == set(self.names)                                    # every entry has its effect rows
         for rows in self.entries.values():
             for row in rows:
                 assert row.how is not None and row.point in self.points and row.session in ("ends", "keeps")
-        return names, exported
 
     def build_c_demo(self, tmp_path):
         from bioen_amd import _lib

@@ -17,7 +17,13 @@ HEADER = os.path.join(ROOT, "include", "bioen_hip.h")
 def declared_functions():
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(bioen_hip_\w+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(bioen_\w+)\s*\(", src)))
+
+
+def defined_dynamic_symbols():
+    from bioen_amd import _lib
+    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
+    return set(line.split()[-1] for line in out.splitlines() if line.strip())
 
 
 def test_library_is_built_and_loads():
@@ -28,25 +34,26 @@ def test_library_is_built_and_loads():
 
 
 def test_every_declared_symbol_is_exported_and_bound():
+    """the ABI is ONE set of names: what include/bioen_hip.h declares, what _lib._SIGNATURES binds and what the library
+    exports under bioen_* are equal -- a new entry is a declaration there and a line there, and no edit here"""
     from bioen_amd import _lib
-    names = declared_functions()
-    assert len(names) >= 25
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    exported = set(line.split()[-1] for line in out.splitlines() if line.strip())
-    missing = [n for n in names if n not in exported]
-    assert not missing, "declared in bioen_hip.h but not exported: %s" % missing
-    unbound = [n for n in names if n not in _lib.exported_symbols()]
-    assert not unbound, "declared in bioen_hip.h but not bound in _lib.py: %s" % unbound
-    extra = [n for n in _lib.exported_symbols() if n not in names]
-    assert not extra, "bound in _lib.py but not declared in the header: %s" % extra
+    declared = set(declared_functions())
+    bound = set(_lib.exported_symbols())
+    exported = set(n for n in defined_dynamic_symbols() if n.startswith("bioen_"))
+    assert not declared - exported, "declared in bioen_hip.h but not exported: %s" % sorted(declared - exported)
+    assert not declared - bound, "declared in bioen_hip.h but not bound in _lib.py: %s" % sorted(declared - bound)
+    assert not bound - declared, "bound in _lib.py but not declared in the header: %s" % sorted(bound - declared)
+    assert not exported - declared, "exported by the library but not declared in the header: %s" % sorted(exported - declared)
+    assert declared == bound == exported and len(declared) >= 86
+    L = _lib.lib()
+    for n in sorted(bound):
+        assert getattr(L, n).argtypes == _lib._SIGNATURES[n][1], n
 
 
 def test_only_the_abi_is_exported_under_c_names():
     """every defined dynamic symbol that is neither C++-mangled (_Z...) nor the toolchain's (__...) is an entry of the
     C ABI: a helper that leaks out under a plain C name can be interposed by any other object in the process"""
-    from bioen_amd import _lib
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    names = set(line.split()[-1] for line in out.splitlines() if line.strip())
+    names = defined_dynamic_symbols()
     stray = sorted(n for n in names if not n.startswith(("_Z", "__", "bioen_")))
     assert not stray, "exported under C names without being part of the ABI: %s" % stray
 

@@ -1,12 +1,14 @@
-"""The second public header, include/bioen_hip_forces_hessp.h, held to the rules of tests/abi_header_rules.py: what it
-declares is exported and bound (in _lib.py's second table), it is plain C and a C caller links against it, and every entry
-has an effect row that is exercised on the GPU."""
+"""The Hessian-vector products of the forces method, bioen_hip_forces_hessp, held to the rules of tests/entry_rules.py: the
+entry is declared in include/bioen_hip.h, a C caller compiles against it as plain C and links, and the entry has its effect
+rows (tests/test_entry_effects.py reads them from here), exercised on the GPU."""
 import pytest
 
-from abi_header_rules import HeaderRules, bioen_amd, f, v      # noqa: F401 -- bioen_amd is the GPU tests' fixture
-from test_entry_effects import P, Row
+from entry_rules import EntryRules, P, Row, bioen_amd, f, v      # noqa: F401 -- bioen_amd is the GPU tests' fixture
+from test_abi import declared_functions
 
-# the rows of DESIGN section 6c for this header: with forces the call is an evaluation that leaves a new point; without, it
+NAMES = ["bioen_hip_forces_hessp"]
+
+# the rows of DESIGN section 6c for this entry: with forces the call is an evaluation that leaves a new point; without, it
 # serves the kept one
 ENTRIES = {
     "bioen_hip_forces_hessp": [
@@ -15,11 +17,13 @@ ENTRIES = {
     ],
 }
 
-RULES = HeaderRules("bioen_hip_forces_hessp.h", ["bioen_hip_forces_hessp"], "forces_hessp", "c_abi_forces_hessp_demo", ENTRIES)
+RULES = EntryRules(NAMES, "c_abi_forces_hessp_demo", ENTRIES)
 
 
-def test_every_declared_symbol_is_exported_bound_and_classified():
-    RULES.check_declared_exported_bound_and_classified()                  # (the first table is bioen_hip.h's alone: among the rules)
+def test_entries_are_declared_and_classified():
+    """(exported and bound: tests/test_abi.py, for every declared name at once)"""
+    assert not set(NAMES) - set(declared_functions())
+    RULES.check_classified()
 
 
 def test_header_is_plain_c_and_a_c_caller_links(tmp_path):

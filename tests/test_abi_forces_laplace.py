@@ -1,31 +1,14 @@
-"""The seventh public header, include/bioen_hip_forces_laplace.h, held to the rules of tests/abi_header_rules.py: what it
-declares is exported and bound (in _lib.py's seventh table, and in no other), it is plain C and a C caller links against
-it, and every entry has its effect rows, exercised on the GPU.  Its entries are bioen_laplace_*: the
-bioen_hip_* names are closed over the six earlier tables (tests/test_abi_forces_newton.py), so the rules' pattern is
-widened here."""
-import re
-
+"""The Laplace error bars of the forces method without leaving the device, bioen_laplace_*, held to the rules of
+tests/entry_rules.py: the entries are declared in include/bioen_hip.h, a C caller compiles against it as plain C and links,
+and every entry has its effect rows (tests/test_entry_effects.py reads them from here), exercised on the
+GPU."""
 import numpy as np
 import pytest
 
-from abi_header_rules import HeaderRules, bioen_amd, f      # noqa: F401 -- bioen_amd is the GPU tests' fixture
-from test_entry_effects import P, Row
+from entry_rules import EntryRules, P, Row, bioen_amd, f      # noqa: F401 -- bioen_amd is the GPU tests' fixture
+from test_abi import declared_functions
 
-PREFIX = "bioen_laplace_"
 NAMES = ["bioen_laplace_forces", "bioen_laplace_forces_inverse"]
-
-
-class LaplaceRules(HeaderRules):
-    """the header's entries carry PREFIX where the rules expect bioen_hip_"""
-
-    def declared_functions(self):
-        src = re.sub(r"/\*.*?\*/", "", open(self.header).read(), flags=re.S)
-        assert not re.findall(r"\b(bioen_hip_\w+)\s*\(", src)            # nothing of the closed namespace is declared here
-        return sorted(set(re.findall(r"\b(%s\w+)\s*\(" % PREFIX, src)))
-
-    def rows(self):
-        return [pytest.param(row, id="%s-%d" % (name[len(PREFIX):], i))
-                for name in self.names for i, row in enumerate(self.entries[name])]
 
 
 def _spd():
@@ -34,7 +17,7 @@ def _spd():
     return B.dot(B.T) / m + np.eye(m)
 
 
-# the rows of DESIGN section 6c for this header: the inverse keeps point and session (with A=None it needs a forces point);
+# the rows of DESIGN section 6c for these entries: the inverse keeps point and session (with A=None it needs a forces point);
 # the error bars with forces are an evaluation that leaves a new point, without they serve the kept one
 ENTRIES = {
     "bioen_laplace_forces_inverse": [
@@ -47,23 +30,13 @@ ENTRIES = {
     ],
 }
 
-RULES = LaplaceRules("bioen_hip_forces_laplace.h", NAMES, "forces_laplace", "c_abi_forces_laplace_demo", ENTRIES,
-                     points=("keeps", "sets", "needs"))
+RULES = EntryRules(NAMES, "c_abi_forces_laplace_demo", ENTRIES, points=("keeps", "sets", "needs"))
 
 
-def test_every_declared_symbol_is_exported_bound_and_classified():
-    from bioen_amd import _lib
-    names, exported = RULES.check_declared_exported_bound_and_classified()
-    others = (_lib.exported_symbols(), _lib.exported_symbols_forces_hessp(), _lib.exported_symbols_forces_gram(),
-              _lib.exported_symbols_forces_colquad(), _lib.exported_symbols_forces_gram_bf16(),
-              _lib.exported_symbols_forces_newton())
-    for table in others:                                                  # the other six tables are their headers' alone
-        assert not set(names) & set(table)
-        assert not [n for n in table if n.startswith(PREFIX)]
-    # the other direction: every bioen_hip_* or bioen_laplace_* symbol the library exports is bound in one of the seven tables
-    bound = set(names).union(*others)
-    assert not sorted(n for n in exported if n.startswith(("bioen_hip_", PREFIX)) and n not in bound)
-    assert sorted(n for n in exported if n.startswith(PREFIX)) == NAMES
+def test_entries_are_declared_and_classified():
+    """(exported and bound: tests/test_abi.py, for every declared name at once)"""
+    assert not set(NAMES) - set(declared_functions())
+    RULES.check_classified()
 
 
 def test_header_is_plain_c_and_a_c_caller_links(tmp_path):

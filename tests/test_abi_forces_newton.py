@@ -1,7 +1,7 @@
-"""The sixth public header, include/bioen_hip_forces_newton.h, held to the rules of tests/abi_header_rules.py: what it
-declares is exported and bound (in _lib.py's sixth table, and in no other), it is plain C and a C caller links against it,
-its two structs have the layout of the ctypes classes, and every entry has an effect row that is
-exercised on the GPU."""
+"""The device-resident Newton minimizer of the forces method, its factorisation and solves, held to the rules of
+tests/entry_rules.py: the entries are declared in include/bioen_hip.h, a C caller compiles against it as plain C and links,
+their two structs have the layout of the ctypes classes, and every entry has its effect rows (DESIGN section 6c;
+tests/test_entry_effects.py reads them from here), exercised on the GPU."""
 import ctypes as C
 import os
 import subprocess
@@ -9,9 +9,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from abi_header_rules import HeaderRules, bioen_amd, f, v      # noqa: F401 -- bioen_amd is the GPU tests' fixture
 from conftest import ROOT
-from test_entry_effects import P, Row
+from entry_rules import EntryRules, P, Row, bioen_amd, f, v      # noqa: F401 -- bioen_amd is the GPU tests' fixture
+from test_abi import declared_functions
 
 NAMES = ["bioen_hip_forces_newton_factor", "bioen_hip_forces_newton_solve", "bioen_hip_opt_newton_forces"]
 
@@ -27,7 +27,7 @@ def _factor_then_solve(c):
     c.forces_newton_solve(v())
 
 
-# the rows of DESIGN section 6c for this header: the factorisation and the solve keep point and session (with A=None the
+# the rows of DESIGN section 6c for these entries: the factorisation and the solve keep point and session (with A=None the
 # factorisation needs a forces point); the minimizer evaluates, and leaves its optimum as the new point
 ENTRIES = {
     "bioen_hip_forces_newton_factor": [
@@ -41,28 +41,19 @@ ENTRIES = {
 }
 
 
-RULES = HeaderRules("bioen_hip_forces_newton.h", NAMES, "forces_newton", "c_abi_forces_newton_demo", ENTRIES,
-                    points=("keeps", "sets", "needs"))
+RULES = EntryRules(NAMES, "c_abi_forces_newton_demo", ENTRIES, points=("keeps", "sets", "needs"))
 
 
-def test_every_declared_symbol_is_exported_bound_and_classified():
-    from bioen_amd import _lib
-    names, exported = RULES.check_declared_exported_bound_and_classified()
-    others = (_lib.exported_symbols(), _lib.exported_symbols_forces_hessp(), _lib.exported_symbols_forces_gram(),
-              _lib.exported_symbols_forces_colquad(), _lib.exported_symbols_forces_gram_bf16())
-    for table in others:                                                  # ... and the other five tables are their headers' alone
-        assert not set(names) & set(table)
-    assert [t for t in others[1:]] == [["bioen_hip_forces_hessp"], ["bioen_hip_forces_gram"], ["bioen_hip_forces_colquad"],
-                                       ["bioen_hip_forces_gram_bf16"]]
-    # the other direction: every bioen_hip_* symbol the library exports is declared in one of the six tables
-    bound = set(names).union(*others)
-    assert not sorted(n for n in exported if n.startswith("bioen_hip_") and n not in bound)
+def test_entries_are_declared_and_classified():
+    """(exported and bound: tests/test_abi.py, for every declared name at once)"""
+    assert not set(NAMES) - set(declared_functions())
+    RULES.check_classified()
 
 
 STRUCT_PROBE = r"""
 #include <stddef.h>
 #include <stdio.h>
-#include "bioen_hip_forces_newton.h"
+#include "bioen_hip.h"
 #define F(T, f) printf(#T "." #f " %zu\n", offsetof(T, f))
 int main(void) {
     printf("bioen_newton_config %zu\nbioen_newton_result %zu\n", sizeof(bioen_newton_config), sizeof(bioen_newton_result));

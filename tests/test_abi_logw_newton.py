@@ -1,43 +1,27 @@
-"""The eighth public header, include/bioen_hip_logw_newton.h, held to the rules of tests/abi_header_rules.py: what it
-declares is exported and bound (in _lib.py's table _SIGNATURES_LOGW_NEWTON, and in no other), it is plain C and a C caller
-links against it, its two structs have the layout of the ctypes classes, and every entry has its effect rows (DESIGN section
-6c), exercised on the GPU.  Its entries are bioen_logwn_*: the bioen_hip_* and bioen_laplace_* names are closed over the
-seven earlier tables.  The point these entries set and need is a LOG-WEIGHTS point, so the check of the effect on the point
-is this file's own (the rules' one starts from a forces point)."""
+"""The log-weights method's dual Newton minimizer and the covariance it is built on, bioen_logwn_*, held to the rules of
+tests/entry_rules.py: the entries are declared in include/bioen_hip.h, a C caller compiles against it as plain C and links,
+their two structs have the layout of the ctypes classes, and every entry has its effect rows (DESIGN section 6c;
+tests/test_entry_effects.py reads them from here), exercised on the GPU.  The point these entries set and need is a
+LOG-WEIGHTS point, so the check of the effect on the point is this file's own (the rules' one starts from a forces point)."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
-from abi_header_rules import HeaderRules, bioen_amd      # noqa: F401 -- bioen_amd is the GPU tests' fixture
 from conftest import ROOT
-from test_entry_effects import P, Row, estate
+from entry_rules import EntryRules, P, Row, bioen_amd, estate      # noqa: F401 -- bioen_amd is the GPU tests' fixture
+from test_abi import declared_functions
 
-PREFIX = "bioen_logwn_"
 NAMES = ["bioen_logwn_cov", "bioen_logwn_opt"]
-
-
-class LogwNewtonRules(HeaderRules):
-    """the header's entries carry PREFIX where the rules expect bioen_hip_"""
-
-    def declared_functions(self):
-        src = re.sub(r"/\*.*?\*/", "", open(self.header).read(), flags=re.S)
-        assert not re.findall(r"\b(bioen_(?:hip|laplace)_\w+)\s*\(", src)      # nothing of the closed namespaces is declared here
-        return sorted(set(re.findall(r"\b(%s\w+)\s*\(" % PREFIX, src)))
-
-    def rows(self):
-        return [pytest.param(row, id="%s-%d" % (name[len(PREFIX):], i))
-                for name in self.names for i, row in enumerate(self.entries[name])]
 
 
 def _p():
     return P.get()
 
 
-# the rows of DESIGN section 6c for this header: the covariance with g is an evaluation that leaves a new point, without it
+# the rows of DESIGN section 6c for these entries: the covariance with g is an evaluation that leaves a new point, without it
 # serves the kept log-weights point; the minimizer evaluates, and leaves its optimum as the new point
 ENTRIES = {
     "bioen_logwn_cov": [
@@ -49,26 +33,19 @@ ENTRIES = {
     ],
 }
 
-RULES = LogwNewtonRules("bioen_hip_logw_newton.h", NAMES, "logw_newton", "c_abi_logw_newton_demo", ENTRIES,
-                        points=("sets", "needs"))
+RULES = EntryRules(NAMES, "c_abi_logw_newton_demo", ENTRIES, points=("sets", "needs"))
 
 
-def test_every_declared_symbol_is_exported_bound_and_classified():
-    from bioen_amd import _lib
-    names, exported = RULES.check_declared_exported_bound_and_classified()
-    others = (_lib.exported_symbols(), _lib.exported_symbols_forces_hessp(), _lib.exported_symbols_forces_gram(),
-              _lib.exported_symbols_forces_colquad(), _lib.exported_symbols_forces_gram_bf16(),
-              _lib.exported_symbols_forces_newton(), _lib.exported_symbols_forces_laplace())
-    for table in others:                                                  # the other seven tables are their headers' alone
-        assert not set(names) & set(table)
-        assert not [n for n in table if n.startswith(PREFIX)]
-    assert sorted(n for n in exported if n.startswith(PREFIX)) == NAMES    # ... and the library exports no other bioen_logwn_*
+def test_entries_are_declared_and_classified():
+    """(exported and bound: tests/test_abi.py, for every declared name at once)"""
+    assert not set(NAMES) - set(declared_functions())
+    RULES.check_classified()
 
 
 STRUCT_PROBE = r"""
 #include <stddef.h>
 #include <stdio.h>
-#include "bioen_hip_logw_newton.h"
+#include "bioen_hip.h"
 #define F(T, f) printf(#T "." #f " %zu\n", offsetof(T, f))
 int main(void) {
     printf("bioen_logwn_config %zu\nbioen_logwn_result %zu\n", sizeof(bioen_logwn_config), sizeof(bioen_logwn_result));

@@ -1,46 +1,26 @@
 """What every entry of the C ABI does to the two pieces of state other calls must respect: the point of
-the Hessian-vector products and the dense BFGS session.  ENTRIES below is the whole rule, one row per entry that takes a
-context; the CPU test keeps it complete against include/bioen_hip.h, the GPU tests check every row that one process on one
-GPU can run.  The rows were written from the sources BEFORE the entries got their common guard and hold for both."""
+the Hessian-vector products and the dense BFGS session.  One row per entry that takes a context: ENTRIES below, and the
+ENTRIES of every tests/test_abi_<feature>.py (found by glob: a new feature brings its rows in a new file of that name, and
+nothing here is edited); the CPU test keeps their union complete against include/bioen_hip.h, the GPU tests here check
+every row of ENTRIES below that one process on one GPU can run, the feature files theirs.  The rows were written from the
+sources BEFORE the entries got their common guard and hold for both."""
 import ctypes as C
+import glob
+import importlib.util
 import os
 import re
-from collections import namedtuple
+import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, LBFGS_DEFAULTS, load_golden
+from conftest import ROOT, LBFGS_DEFAULTS
+from entry_rules import ALPHA, BETA, P, Row, estate
 
 HEADER = os.path.join(ROOT, "include", "bioen_hip.h")
 
-# point:   keeps | drops | sets (leaves a new one) | needs (fails without one, keeps it)
-# session: keeps | ends | needs (fails without one, keeps it; closes=True: its regular end) | starts
-# how:     the call on a bioen_amd.Context (the raw binding where it has no method); None + why: not runnable in one process on one GPU
-# prepare: what a live session (or the context) needs before the call can succeed
-Row = namedtuple("Row", "point session how prepare closes why", defaults=(None, False, None))
-
-ALPHA, BETA = 1e-3, 2e-3           # the trial the session is left at; another one
 LBFGS_SHORT = dict(LBFGS_DEFAULTS, max_iterations=3)
 GSL_SHORT = dict(step_size=0.01, tol=0.1, max_iterations=2)
-
-
-class P(object):
-    """the problem of the tests: synth_logw_M64xN2000 (state logic: the shape does not matter)"""
-    _d = None
-
-    @classmethod
-    def get(cls):
-        if cls._d is None:
-            d = load_golden("synth_logw_M64xN2000.npz")
-            p = cls._d = cls()
-            p.yT, p.YT = d["yTilde"], d["YTilde"].reshape(-1)
-            p.G, p.theta, p.x = d["G"].reshape(-1), float(d["theta"]), d["GInit"].reshape(-1)
-            p.m, p.n = p.yT.shape
-            p.v = np.random.default_rng(1).standard_normal(p.n)
-            p.w0 = np.full(p.n, 1.0 / p.n)
-            p.f0 = np.zeros(p.m)
-        return cls._d
 
 
 def raw(name, *args):
@@ -163,19 +143,40 @@ def declared_entries():
     create functions is a result, not a context to act on"""
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     return {name: re.search(r"\bbioen_hip_ctx\s*\*(?!\s*\*)", args) is not None
-            for name, args in re.findall(r"\b(bioen_hip_\w+)\s*\(([^()]*)\)", src)}
+            for name, args in re.findall(r"\b(bioen_\w+)\s*\(([^()]*)\)", src)}
+
+
+def all_entries():
+    """-> {name: rows}: ENTRIES above with the ENTRIES of every tests/test_abi_<feature>.py, the modules found by glob and
+    loaded by path (one that pytest has imported already is taken as it is); no entry has rows in two places"""
+    out, owner = dict(ENTRIES), dict.fromkeys(ENTRIES, "test_entry_effects")
+    for path in sorted(glob.glob(os.path.join(ROOT, "tests", "test_abi_*.py"))):
+        stem = os.path.splitext(os.path.basename(path))[0]
+        mod = sys.modules.get(stem)
+        if mod is None or os.path.abspath(getattr(mod, "__file__", "")) != os.path.abspath(path):
+            spec = importlib.util.spec_from_file_location(stem, path)
+            mod = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(mod)
+        assert isinstance(getattr(mod, "ENTRIES", None), dict), "%s has no ENTRIES" % stem
+        for name, r in mod.ENTRIES.items():
+            assert name not in out, "%s has rows in %s and in %s" % (name, owner[name], stem)
+            out[name], owner[name] = r, stem
+    return out
 
 
 def test_every_entry_is_classified():
     decl = declared_entries()
-    assert len(decl) >= 70 and decl["bioen_hip_logw_fdf"] and not decl["bioen_hip_ctx_create"]
+    assert decl["bioen_hip_logw_fdf"] and not decl["bioen_hip_ctx_create"]
     with_ctx = {n for n, takes in decl.items() if takes}
-    assert not with_ctx - set(ENTRIES), "takes a context, but has no row in ENTRIES: %s" % sorted(with_ctx - set(ENTRIES))
+    entries = all_entries()
+    assert not with_ctx - set(entries), "takes a context, but has no row in an ENTRIES (here or in a tests/test_abi_*.py): %s" % sorted(
+        with_ctx - set(entries))
     assert not set(decl) - with_ctx - NO_CONTEXT, "not in NO_CONTEXT: %s" % sorted(set(decl) - with_ctx - NO_CONTEXT)
-    assert not set(ENTRIES) - with_ctx, "in ENTRIES, but no declared entry with a context: %s" % sorted(set(ENTRIES) - with_ctx)
+    assert not set(entries) - with_ctx, "in ENTRIES, but no declared entry with a context: %s" % sorted(set(entries) - with_ctx)
     assert not NO_CONTEXT - (set(decl) - with_ctx), "in NO_CONTEXT, but no declared entry without a context: %s" % sorted(
         NO_CONTEXT - (set(decl) - with_ctx))
-    for name, r in ENTRIES.items():
+    assert len(decl) >= 86          # (after the comparisons, so that an entry that went missing is named by them)
+    for name, r in entries.items():     # (a feature file holds its own rows to narrower conditions besides: EntryRules.check_classified)
         for row in (r if isinstance(r, list) else (r,)):
             assert row.point in ("keeps", "drops", "sets", "needs") and row.session in ("keeps", "ends", "needs", "starts")
             assert (row.how is None) == (row.why is not None), name
@@ -188,13 +189,6 @@ def bioen_amd():
     import bioen_amd
     assert bioen_amd.device_count() >= 1
     return bioen_amd
-
-
-def estate(call, *needles):
-    from bioen_amd._lib import BioenHipError
-    with pytest.raises(BioenHipError) as e:
-        call()
-    assert "(-6)" in str(e.value) and all(s in str(e.value) for s in needles), str(e.value)
 
 
 @pytest.mark.gpu
