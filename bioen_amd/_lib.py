@@ -70,8 +70,16 @@ class LogwNewtonResult(C.Structure):
                 ("iterations", C.c_int), ("evaluations", C.c_int), ("factorisations", C.c_int)]
 
 
+class LogwNewtonSeriesResult(C.Structure):
+    # bioen_logwn_series_result (include/bioen_hip.h)
+    _fields_ = [("fmin", C.c_double), ("gmax", C.c_double), ("wmax", C.c_double), ("status", C.c_int),
+                ("iterations", C.c_int), ("evaluations", C.c_int), ("factorisations", C.c_int), ("bf16_passes", C.c_int),
+                ("switched", C.c_int)]
+
+
 # the dual Newton minimizer's constants (log_weights.dual_newton_bioen_log_posterior_base uses the same)
 LOGW_NEWTON_DEFAULTS = dict(gtol=1e-6, max_iterations=200, armijo=1e-4, floor_ulps=8.0, max_halvings=60)
+LOGW_NEWTON_SOURCES = ("gram", "gram_bf16")      # the covariance of the step: the FP64 pass | the split-BF16 one
 
 
 # the Newton minimizer's damping constants (forces.newton_bioen_log_posterior_base uses the same)
@@ -192,6 +200,9 @@ _SIGNATURES = {
     # log-weights method: the dual Newton minimizer and the covariance it is built on
     "bioen_logwn_cov": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp]),
     "bioen_logwn_opt": (C.c_int, [ctx_p, dp, dp, C.c_double, C.POINTER(LogwNewtonConfig), dp, C.POINTER(LogwNewtonResult)]),
+    "bioen_logwn_cov_bf16": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp]),
+    "bioen_logwn_series": (C.c_int, [ctx_p, dp, dp, dp, C.c_int, C.POINTER(LogwNewtonConfig), C.c_int, C.c_int, dp,
+                                     C.POINTER(LogwNewtonSeriesResult)]),
 }
 
 _lib = None
@@ -285,8 +296,16 @@ def newton_source(value):
     return NEWTON_SOURCES.index(v)
 
 
+def logw_newton_source(value):
+    """the dual Newton minimizer's covariance source, checked: "gram" | "gram_bf16" -> 0 | 1"""
+    v = str(value).lower()
+    if v not in LOGW_NEWTON_SOURCES:
+        raise RuntimeError("dual_newton:hessian=" + v + " not recognized (valid values = 'gram', 'gram_bf16')")
+    return LOGW_NEWTON_SOURCES.index(v)
+
+
 def logw_newton_config(params):
-    """params (a dict; missing keys take LOGW_NEWTON_DEFAULTS) -> LogwNewtonConfig"""
+    """params (a dict; missing keys take LOGW_NEWTON_DEFAULTS; "hessian" and "series" are not the struct's) -> LogwNewtonConfig"""
     p = dict(LOGW_NEWTON_DEFAULTS, **(params or {}))
     return LogwNewtonConfig(float(p["gtol"]), float(p["armijo"]), float(p["floor_ulps"]), int(p["max_iterations"]),
                             int(p["max_halvings"]))
@@ -659,6 +678,8 @@ class Context(object):
         exhausted at the rounding floor of f, 3: step exhausted), fmin, gmax, wmax, iterations, evaluations,
         factorisations).  g is in the gauge the steps leave it in: compare weights.  The returned point is the context's
         kept point: logw_cov() and logw_hessp(v) right after serve it."""
+        if logw_newton_source((params or {}).get("hessian", "gram")):       # "gram_bf16": a series of one theta
+            return self.opt_dual_newton_logw_series([theta], g0, G, params, hessian="gram_bf16")[0]
         g0, G = self._nvec(g0, "g0"), self._nvec(G, "G")
         cfg = logw_newton_config(params)
         out = np.empty(self.n)
@@ -666,6 +687,33 @@ class Context(object):
         check(lib().bioen_logwn_opt(self._h, ptr(g0), ptr(G), float(theta), C.byref(cfg), ptr(out), C.byref(res)))
         return dict(g=out, status=res.status, fmin=res.fmin, gmax=res.gmax, wmax=res.wmax, iterations=res.iterations,
                     evaluations=res.evaluations, factorisations=res.factorisations)
+
+    def logw_cov_bf16(self, g=None, G=None, theta=None, cov=True):
+        """logw_cov with the M x M x N product from split-BF16 operands on the BF16 matrix cores (bioen_logwn_cov_bf16;
+        DESIGN 6k): the covariance the dual Newton loop's hessian="gram_bf16" factorises.  Call shape, point semantics,
+        refusals and buffer are logw_cov's; f and grad are its bits; |C~ - C|_ik <= 3 * 2^-16 sqrt(G'_ii G'_kk)."""
+        out = self._gram(lib().bioen_logwn_cov_bf16, "logw_cov_bf16", "N", ("g", "G"), g, G, theta, cov=cov)
+        return out[0] if g is None else out
+
+    def opt_dual_newton_logw_series(self, thetas, g0, G, params=None, hessian="gram", warm=True):
+        """opt_dual_newton_logw for the thetas in the order given, in one call (bioen_logwn_series): G goes up
+        once, the vectors stay in HBM, warm=True starts theta k at the point theta k - 1 returned (False: every theta at g0).
+        hessian: "gram" (the FP64 covariance: bit for bit the chained / single calls) or "gram_bf16" (the split-BF16 pass;
+        a step rejected at the rounding floor sends that theta's run over to the FP64 pass, once); params["hessian"], if
+        present, wins.  -> a list of opt_dual_newton_logw's dicts plus bf16_passes and switched.  A theta that ends with
+        status != 0 does not stop the series.  The last theta's returned point is the context's kept point."""
+        p = dict(params or {})
+        source = logw_newton_source(p.get("hessian", hessian))
+        th = as_f64(np.asarray(thetas, dtype=np.float64).reshape(-1))
+        g0, G = self._nvec(g0, "g0"), self._nvec(G, "G")
+        cfg = logw_newton_config(p)
+        out = np.empty((max(len(th), 1), self.n))
+        res = (LogwNewtonSeriesResult * max(len(th), 1))()
+        check(lib().bioen_logwn_series(self._h, ptr(g0), ptr(G), ptr(th), int(len(th)), C.byref(cfg), source, int(bool(warm)),
+                                       ptr(out), res))
+        return [dict(g=out[k].copy(), status=r.status, fmin=r.fmin, gmax=r.gmax, wmax=r.wmax, iterations=r.iterations,
+                     evaluations=r.evaluations, factorisations=r.factorisations, bf16_passes=r.bf16_passes,
+                     switched=bool(r.switched)) for k, r in enumerate(res)]
 
     def opt_lbfgs_logw(self, g0, G, theta, params, verbose=False, debug=False, want_weights=True):
         g0, G = self._nvec(g0, "g0"), self._nvec(G, "G")

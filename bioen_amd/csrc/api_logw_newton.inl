@@ -2,7 +2,9 @@
 // its static helpers; kernels: kernels_logw_newton.hip).  N unknowns through an M x M system: C of the kept
 // log-weights point from k_logw_gram, C + theta I factorised and solved by section 6h's kernels (api_forces_newton.inl:
 // fnewton_factor, launch_fnewton_solve), the step from ONE centred adjoint pass on r + z.  Every N-vector stays in HBM; the
-// loop is log_weights.py's dual_newton_bioen_log_posterior_base, decision for decision.  The point is bioen_hip_logw_hessp's:
+// loop is log_weights.py's dual_newton_bioen_log_posterior_base, decision for decision.  DESIGN section 6k: C may come from
+// k_logw_gram_bf16 instead (split-BF16 products; -b, the gradient and every test of the loop stay FP64), and the loop runs a
+// whole theta series behind one call (bioen_logwn_series), warm- or cold-started.  The point is bioen_hip_logw_hessp's:
 // set, kept and refused by api_forces_point.inl's logw_point_prologue / logw_keep_point, the entries guarded by its dense_guard.
 
 namespace bioen {
@@ -22,14 +24,18 @@ static int logwn_keep_point(bioen_hip_ctx* c, double theta, double* f, const cha
     return logwn_copies(c, who);
 }
 
-// C of the kept log-weights point into SCRATCH_LOGW_GRAM, not downloaded; negb (may be NULL): -Yc grad for the solve
-static int logwn_gram(bioen_hip_ctx* c, const double** cov, double* negb) {
+// the covariance's source: the FP64 pass (k_logw_gram) or the split-BF16 one (k_logw_gram_bf16)
+enum LogwnSource : int { LOGWN_FP64 = 0, LOGWN_BF16 = 1 };
+
+// C of the kept log-weights point into SCRATCH_LOGW_GRAM, not downloaded; negb (may be NULL): -Yc grad for the solve (the
+// same bits from either source)
+static int logwn_gram(bioen_hip_ctx* c, int source, const double** cov, double* negb) {
     int rc;
     const GramPlan p = logw_gram_plan(c);
     if ((rc = ensure_scratch(c, SCRATCH_LOGW_GRAM, p.doubles))) return rc;
     double* buf = c->scratch[SCRATCH_LOGW_GRAM].p;
     const ProblemSlot& s0 = c->slot[0];
-    launch_logw_gram(c, p, buf, s0.w, s0.g, s0.scal, c->point_ybar, negb);
+    launch_logw_gram(c, p, buf, s0.w, s0.g, s0.scal, c->point_ybar, negb, source == LOGWN_BF16);
     if ((rc = check_launch())) return rc;
     if (cov) *cov = buf + p.cov_at;
     return 0;
@@ -50,47 +56,50 @@ static int logwn_stats(bioen_hip_ctx* c, double theta, double* gmax, double* wma
     return 0;
 }
 
-}  // namespace bioen
-
-extern "C" int bioen_logwn_cov(bioen_hip_ctx* c, const double* g, const double* G, double theta, double* C, double* f,
-                               double* grad) {
-    if (int rc = enter(c, FX_NONE, __func__)) return rc;      // a call rejected below leaves the point (and the device) alone
+// bioen_logwn_cov and bioen_logwn_cov_bf16: one entry, the source apart
+static int logwn_cov_entry(bioen_hip_ctx* c, const double* g, const double* G, double theta, double* C, double* f, double* grad,
+                           int source, const char* who) {
+    if (int rc = enter(c, FX_NONE, who)) return rc;           // a call rejected below leaves the point (and the device) alone
     if (g && !G) return fail(BIOEN_HIP_EINVAL, "g without G");
     if (!g && !C) return fail(BIOEN_HIP_EINVAL, "nothing to do: no g and no C");
     int rc;
-    if ((rc = dense_guard(c, __func__, kLogwnReasons, fwd_strip_blocks))) return rc;
-    if ((rc = logw_point_prologue(c, g, G, theta, 1, f, grad, __func__, &kLogwnPoint))) return rc;
-    if (g && (rc = logwn_copies(c, __func__))) return rc;
+    if ((rc = dense_guard(c, who, kLogwnReasons, fwd_strip_blocks))) return rc;
+    if ((rc = logw_point_prologue(c, g, G, theta, 1, f, grad, who, &kLogwnPoint))) return rc;
+    if (g && (rc = logwn_copies(c, who))) return rc;
     if (!C) return 0;
     const double* dcov = nullptr;
-    if ((rc = logwn_gram(c, &dcov, nullptr))) return rc;
+    if ((rc = logwn_gram(c, source, &dcov, nullptr))) return rc;
     BIOEN_HIP_CHECK(hipMemcpyAsync(C, dcov, (size_t)c->m * c->m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
     return 0;
 }
 
-extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double* G, double theta,
-                               const bioen_logwn_config* cfg, double* gopt, bioen_logwn_result* res) {
-    if (int rc = enter(c, FX_NONE, __func__)) return rc;
-    if (!g0 || !G || !cfg || !gopt || !res) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+// what bioen_logwn_opt and bioen_logwn_series refuse before the device, the point or a session are touched
+static int logwn_check(const bioen_logwn_config* cfg, const double* thetas, int ntheta, const char* who) {
     if (!(cfg->gtol >= 0.0) || cfg->max_iterations < 0 || cfg->max_halvings < 1 || !(cfg->armijo > 0.0) || !(cfg->floor_ulps >= 0.0))
         return fail(BIOEN_HIP_EINVAL, "bioen_logwn_config: gtol >= 0, max_iterations >= 0, max_halvings >= 1, armijo > 0, floor_ulps >= 0");
+    for (int k = 0; k < ntheta; ++k)
+        if (!(thetas[k] > 0.0) || !std::isfinite(thetas[k]))
+            return fail(BIOEN_HIP_EINVAL, (std::string(who) + " needs theta > 0 (the step divides by theta): use the L-BFGS for theta = 0").c_str());
+    return 0;
+}
+
+// The loop for one theta and one covariance source, from the point slot 0's xp holds (c->fixed = G): DESIGN 6j, and 6k's
+// switch -- with LOGWN_BF16 a step rejected at the rounding floor does not end the run: the kept point is restored and the
+// FP64 pass serves the rest of this theta (once; res->switched).  Leaves the returned point in xp, evaluated and kept; every
+// status returns 0.
+static int logwn_loop(bioen_hip_ctx* c, double theta, const bioen_logwn_config* cfg, int source,
+                      bioen_logwn_series_result* res, const char* who) {
     int rc;
-    if (!(theta > 0.0) || !std::isfinite(theta))
-        return fail(BIOEN_HIP_EINVAL, "bioen_logwn_opt needs theta > 0 (the step divides by theta): use the L-BFGS for theta = 0");
-    if ((rc = dense_guard(c, __func__, kLogwnReasons, fwd_strip_blocks))) return rc;
-    if ((rc = enter(c, FX_EVALUATES, __func__))) return rc;
     const double eps = 2.220446049250313e-16;
     ProblemSlot& s0 = c->slot[0];
-    *res = bioen_logwn_result{};
+    *res = bioen_logwn_series_result{};
     // slot 0: xp = the accepted point, d = the step u, x = the trial (k_trial: x = xp + alpha d), w, g, a, scal = the
     // evaluation's; hp_vec[0] takes the adjoint of r + z
-    if ((rc = upload_n(c, s0.xp, g0))) return rc;
-    if ((rc = upload_n(c, c->fixed, G))) return rc;
     BIOEN_HIP_CHECK(hipMemcpyAsync(s0.x, s0.xp, c->ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     BIOEN_HIP_CHECK(hipMemsetAsync(s0.d, 0, c->ld * sizeof(double), c->stream));
     double f = 0.0, ft = 0.0, gmax = 0.0, wmax = 0.0, cmax = 0.0;
-    if ((rc = logwn_keep_point(c, theta, &f, __func__))) return rc;
+    if ((rc = logwn_keep_point(c, theta, &f, who))) return rc;
     res->evaluations = 1;
     if ((rc = fnewton_buffers(c))) return rc;
     const GramPlan plan = logw_gram_plan(c);
@@ -111,7 +120,8 @@ extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double*
         }
         // 3. C and -b of the kept point (= xp), (C + theta I) z = -b, the operand r + z, its adjoint, u and grad . u
         const double* cov = nullptr;
-        if ((rc = logwn_gram(c, &cov, nb.X))) return rc;
+        if ((rc = logwn_gram(c, source, &cov, nb.X))) return rc;
+        if (source == LOGWN_BF16) ++res->bf16_passes;
         int info = 0;
         if ((rc = fnewton_factor(c, cov, theta, &info, nullptr))) return rc;
         ++res->factorisations;
@@ -123,7 +133,7 @@ extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double*
         launch_logwn_operand(c, nb.X, c->hp_scal);
         int nblk = 0;                                        // (the evaluation has built the copies the adjoint reads)
         if ((rc = choose_logw_passes(c, true, 0, true, &nblk))) return rc;
-        if (nblk <= 0) return fail(BIOEN_HIP_ESTATE, "bioen_logwn_opt needs the strip copies of the matrix");
+        if (nblk <= 0) return fail(BIOEN_HIP_ESTATE, (std::string(who) + " needs the strip copies of the matrix").c_str());
         MVec8 out{}, sc{};
         out.p[0] = c->hp_vec[0];
         sc.p[0] = c->hp_scal;
@@ -138,18 +148,19 @@ extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double*
         BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
         // 4. alpha = 1, 1/2, ...
         double alpha = 1.0, gtmax = 0.0, wtmax = 0.0, ctmax = 0.0;
-        bool accepted = false;
+        bool accepted = false, go_over = false;
         for (int k = 0; k < cfg->max_halvings; ++k) {
             Round r = make_round(c, one, 1, &alpha, &theta);
             launch_trial(c, r);
-            point_drop(c, __func__);
-            if ((rc = logwn_keep_point(c, theta, &ft, __func__))) return rc;
+            point_drop(c, who);
+            if ((rc = logwn_keep_point(c, theta, &ft, who))) return rc;
             ++res->evaluations;
             at_x = 0;
             if ((rc = logwn_stats(c, theta, &gtmax, &wtmax, &ctmax))) return rc;
             const bool floor = std::fabs(alpha * slope) <= cfg->floor_ulps * eps * std::fabs(f);
             if (floor) {
                 if (std::isfinite(ft) && gtmax < gmax) accepted = true;
+                else if (source == LOGWN_BF16) go_over = true;       // 5. the step was the split pass's: FP64 from here on
                 else status = 2;
                 break;
             }
@@ -158,6 +169,17 @@ extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double*
                 break;
             }
             alpha *= 0.5;
+        }
+        if (go_over) {                                       // the kept point again (one evaluation), then C anew
+            source = LOGWN_FP64;
+            res->switched = 1;
+            BIOEN_HIP_CHECK(hipMemcpyAsync(s0.x, s0.xp, c->ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            point_drop(c, who);
+            if ((rc = logwn_keep_point(c, theta, &f, who))) return rc;
+            ++res->evaluations;
+            if ((rc = logwn_stats(c, theta, &gmax, &wmax, &cmax))) return rc;
+            at_x = 1;
+            continue;
         }
         if (!accepted) {
             if (status < 0) status = 3;
@@ -170,16 +192,77 @@ extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double*
     }
     if (!at_x) {                                             // the returned point is the kept one
         BIOEN_HIP_CHECK(hipMemcpyAsync(s0.x, s0.xp, c->ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        point_drop(c, __func__);
-        if ((rc = logwn_keep_point(c, theta, &f, __func__))) return rc;
+        point_drop(c, who);
+        if ((rc = logwn_keep_point(c, theta, &f, who))) return rc;
         ++res->evaluations;
         if ((rc = logwn_stats(c, theta, &gmax, &wmax, &cmax))) return rc;
     }
-    if ((rc = download_n(c, gopt, s0.xp))) return rc;
-    BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
     res->status = status;
     res->fmin = f;
     res->gmax = gmax;
     res->wmax = wmax;
+    return 0;
+}
+
+}  // namespace bioen
+
+extern "C" int bioen_logwn_cov(bioen_hip_ctx* c, const double* g, const double* G, double theta, double* C, double* f,
+                               double* grad) {
+    return logwn_cov_entry(c, g, G, theta, C, f, grad, LOGWN_FP64, __func__);
+}
+
+extern "C" int bioen_logwn_cov_bf16(bioen_hip_ctx* c, const double* g, const double* G, double theta, double* C, double* f,
+                                    double* grad) {
+    return logwn_cov_entry(c, g, G, theta, C, f, grad, LOGWN_BF16, __func__);
+}
+
+extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double* G, double theta,
+                               const bioen_logwn_config* cfg, double* gopt, bioen_logwn_result* res) {
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
+    if (!g0 || !G || !cfg || !gopt || !res) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    int rc;
+    if ((rc = logwn_check(cfg, &theta, 1, __func__))) return rc;
+    if ((rc = dense_guard(c, __func__, kLogwnReasons, fwd_strip_blocks))) return rc;
+    if ((rc = enter(c, FX_EVALUATES, __func__))) return rc;
+    *res = bioen_logwn_result{};
+    if ((rc = upload_n(c, c->slot[0].xp, g0))) return rc;
+    if ((rc = upload_n(c, c->fixed, G))) return rc;
+    bioen_logwn_series_result r;
+    if ((rc = logwn_loop(c, theta, cfg, LOGWN_FP64, &r, __func__))) return rc;
+    if ((rc = download_n(c, gopt, c->slot[0].xp))) return rc;
+    BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
+    res->status = r.status;
+    res->fmin = r.fmin;
+    res->gmax = r.gmax;
+    res->wmax = r.wmax;
+    res->iterations = r.iterations;
+    res->evaluations = r.evaluations;
+    res->factorisations = r.factorisations;
+    return 0;
+}
+
+extern "C" int bioen_logwn_series(bioen_hip_ctx* c, const double* g0, const double* G, const double* thetas, int ntheta,
+                                  const bioen_logwn_config* cfg, int source, int warm, double* gopt,
+                                  bioen_logwn_series_result* results) {
+    if (int rc = enter(c, FX_NONE, __func__)) return rc;
+    if (!g0 || !G || !thetas || !cfg || !gopt || !results) return fail(BIOEN_HIP_EINVAL, "NULL argument");
+    if (ntheta < 1) return fail(BIOEN_HIP_EINVAL, "bioen_logwn_series needs ntheta >= 1");
+    if (source != LOGWN_FP64 && source != LOGWN_BF16) return fail(BIOEN_HIP_EINVAL, "bioen_logwn_series: source is 0 (FP64) or 1 (split BF16)");
+    if (warm != 0 && warm != 1) return fail(BIOEN_HIP_EINVAL, "bioen_logwn_series: warm is 0 or 1");
+    int rc;
+    if ((rc = logwn_check(cfg, thetas, ntheta, __func__))) return rc;
+    if ((rc = dense_guard(c, __func__, kLogwnReasons, fwd_strip_blocks))) return rc;
+    if ((rc = enter(c, FX_EVALUATES, __func__))) return rc;
+    ProblemSlot& s0 = c->slot[0];
+    if ((rc = upload_n(c, s0.xp, g0))) return rc;
+    if ((rc = upload_n(c, c->fixed, G))) return rc;
+    // cold: g0 waits in slot 0's gp, which neither the evaluations nor the step write
+    if (!warm) BIOEN_HIP_CHECK(hipMemcpyAsync(s0.gp, s0.xp, c->ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    for (int k = 0; k < ntheta; ++k) {
+        if (!warm && k > 0) BIOEN_HIP_CHECK(hipMemcpyAsync(s0.xp, s0.gp, c->ld * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if ((rc = logwn_loop(c, thetas[k], cfg, source, &results[k], __func__))) return rc;
+        if ((rc = download_n(c, gopt + (size_t)k * c->n, s0.xp))) return rc;
+        BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
     return 0;
 }

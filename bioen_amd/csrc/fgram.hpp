@@ -3,7 +3,8 @@
 // (set, sub-tile) it owns, its rows' centres, the matrix half of a strip's fetch, the row sums on their way out.
 // The FP64 pass itself is here too, once (fgram_pass): k_forces_gram and k_logw_gram are its two instances, each with a
 // POINT that says how many matrices a wave accumulates and how a column's weights come from what the point keeps.  The
-// BF16 kernel keeps a loop of its own: its weights arrive by shuffles and its operands are split.
+// BF16 kernels keep loops of their own: their weights arrive by shuffles and their operands are split (the split and the
+// instruction are here, once; one templated loop for both did not leave k_forces_gram_bf16's code object as it was: DESIGN 6k).
 #pragma once
 
 #include "strip.hpp"
@@ -125,6 +126,29 @@ __device__ __forceinline__ void fgram_store_row_sums(const FGramArgs& q, const F
         const int row = w.ra + 16 * h + lr;
         if (lq == 0) q.partial[(size_t)w.set * q.set_stride + q.rows_at + row] = row < q.mps ? t : 0.0;
     }
+}
+
+// ---- the split-BF16 passes' operands (k_forces_gram_bf16, k_logw_gram_bf16) ------------------------------------
+typedef float fl4 __attribute__((ext_vector_type(4)));
+typedef short bh4 __attribute__((ext_vector_type(4)));      // four bfloat16: an operand fragment of the 16-deep instruction
+typedef unsigned u2v __attribute__((ext_vector_type(2)));   // the same two registers as they are filled: elements (0, 1) | (2, 3)
+typedef __bf16 bfp __attribute__((ext_vector_type(2)));
+typedef float flp __attribute__((ext_vector_type(2)));
+
+// two floats -> two bfloat16 in one register (v0 in the low half), round to nearest even: v_cvt_pk_bf16_f32
+__device__ __forceinline__ unsigned bf_pack(float v0, float v1) {
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(flp{v0, v1}, bfp));
+}
+
+// v0, v1 = hi + lo + (what the split drops), both bfloat16: a register of two his and one of two los -- half a fragment
+__device__ __forceinline__ void bf_split2(double v0, double v1, unsigned& hi, unsigned& lo) {
+    const float f0 = (float)v0, f1 = (float)v1;
+    hi = bf_pack(f0, f1);
+    lo = bf_pack(f0 - __uint_as_float(hi << 16), f1 - __uint_as_float(hi & 0xffff0000u));       // exact in f32
+}
+
+__device__ __forceinline__ fl4 mfma16(u2v a, u2v b, fl4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(bh4, a), __builtin_bit_cast(bh4, b), c, 0, 0, 0);
 }
 
 // ---- the FP64 pass -------------------------------------------------------------------------------------------------------

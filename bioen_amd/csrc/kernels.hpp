@@ -212,9 +212,10 @@ void launch_fgram_sum_sets(bioen_hip_ctx* c, double* buf, size_t set_stride, int
 // vector kernels of the loop around it --------------------------------------------------------------------------------
 enum LogwnScal : int { LN_GMAX = 0, LN_WMAX, LN_GAMMA, LN_SLOPE, kLogwnScal = 8 };
 GramPlan logw_gram_plan(const bioen_hip_ctx* c);
-// the sets, their sum, C (affine model: S C S) at buf + cov_at; negb (may be NULL, mp doubles) <- -Yc grad (affine: S .)
+// the sets, their sum, C (affine model: S C S) at buf + cov_at; negb (may be NULL, mp doubles) <- -Yc grad (affine: S .);
+// bf16: the sets from k_logw_gram_bf16 (split-BF16 products; -b keeps k_logw_gram's bits), everything behind them unchanged
 void launch_logw_gram(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* e, const double* grad,
-                      const double* pscal, const double* ybar, double* negb);
+                      const double* pscal, const double* ybar, double* negb, bool bf16);
 // operand <- r_c + row_scale o z (K = 1: the centred adjoint's operand), its constants S_B0, S_UY into scal
 void launch_logwn_operand(bioen_hip_ctx* c, const double* z, double* scal);
 // out[LN_GMAX, LN_WMAX, LN_GAMMA] <- max |grad|, max w, max |gamma|, gamma = theta (x - G - P) + a, of the evaluated slot

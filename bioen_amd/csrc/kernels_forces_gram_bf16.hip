@@ -17,28 +17,7 @@
 
 namespace bioen {
 
-typedef float fl4 __attribute__((ext_vector_type(4)));
-typedef short bh4 __attribute__((ext_vector_type(4)));      // four bfloat16: an operand fragment of the 16-deep instruction
-typedef unsigned u2v __attribute__((ext_vector_type(2)));   // the same two registers as they are filled: elements (0, 1) | (2, 3)
-typedef __bf16 bfp __attribute__((ext_vector_type(2)));
-typedef float flp __attribute__((ext_vector_type(2)));
-
-// two floats -> two bfloat16 in one register (v0 in the low half), round to nearest even: v_cvt_pk_bf16_f32
-__device__ __forceinline__ unsigned bf_pack(float v0, float v1) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(flp{v0, v1}, bfp));
-}
-
-// v0, v1 = hi + lo + (what the split drops), both bfloat16: a register of two his and one of two los -- half a fragment
-__device__ __forceinline__ void bf_split2(double v0, double v1, unsigned& hi, unsigned& lo) {
-    const float f0 = (float)v0, f1 = (float)v1;
-    hi = bf_pack(f0, f1);
-    lo = bf_pack(f0 - __uint_as_float(hi << 16), f1 - __uint_as_float(hi & 0xffff0000u));       // exact in f32
-}
-
-__device__ __forceinline__ fl4 mfma16(u2v a, u2v b, fl4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(bh4, a), __builtin_bit_cast(bh4, b), c, 0, 0, 0);
-}
-
+// (the split and the 16-deep instruction -- bf_split2, mfma16 -- are fgram.hpp's, shared with k_logw_gram_bf16)
 struct FGram16Regs {
     d2 a[kWaveRows / 8];
     d2 b[kWaveRows / 8];

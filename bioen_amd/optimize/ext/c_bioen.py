@@ -435,6 +435,30 @@ def bioen_opt_dual_newton_logw(g, G, yTilde, YTilde, theta, params):
     return res["g"], res["fmin"]
 
 
+def bioen_opt_dual_newton_logw_series(g, G, yTilde, YTilde, thetas, params):
+    """-> ([gopt[n]] * ntheta, [fmin] * ntheta): the dual Newton minimizer for a theta series in one device call
+    (Context.opt_dual_newton_logw_series), in the order given; warm-started unless params["params"]["series"] is "cold".
+    Every theta runs; then the first status != 0 raises RuntimeError naming its theta, as bioen_opt_dual_newton_logw does.
+    last_opt_info: the list of result dicts."""
+    global last_opt_info
+    p = dict(params["params"])
+    mode = str(p.pop("series", "warm")).lower()
+    if mode not in ("warm", "cold"):
+        raise RuntimeError("dual_newton:series=" + mode + " not recognized (valid values = 'warm', 'cold')")
+    ctx, cached = _context_for(yTilde, YTilde)
+    try:
+        res = ctx.opt_dual_newton_logw_series([float(t) for t in thetas], np.asarray(g, dtype=np.float64).reshape(-1),
+                                              np.asarray(G, dtype=np.float64).reshape(-1), p, warm=(mode == "warm"))
+    finally:
+        _release(ctx, cached)
+    last_opt_info = res
+    for t, r in zip(thetas, res):
+        if r["status"] != 0:
+            raise RuntimeError("bioen_opt_dual_newton_logw_series: theta = %r: return code %d after %d iterations, "
+                               "max|grad| = %.3g, max w = %.3g" % (float(t), r["status"], r["iterations"], r["gmax"], r["wmax"]))
+    return [r["g"] for r in res], [r["fmin"] for r in res]
+
+
 def bioen_opt_newton_forces(forces, w0, yTilde, YTilde, theta, params):
     """-> (forces_opt[m], fmin): the device-resident Newton minimizer (Context.opt_newton_forces).  Status 0 (max|g| <=
     gtol) and 2 (at the minimum to the rounding of f) return; 1 (max_iterations) and 3 (the damping left its range) raise

@@ -198,12 +198,34 @@ def dual_newton_covariance(p, yT):
     return (Yc * p["w"]).dot(Yc.T)
 
 
-def dual_newton_step(p, yT, theta):
-    """(u, z) at a point of _dual_newton_point: one covariance, one Cholesky factorisation of C + theta I (SPD for
-    every theta > 0), one centred forward pass on grad, one centred adjoint pass on r + z"""
+def dual_newton_covariance_bf16(p, yT, centre):
+    """The numpy restatement of Context.logw_cov_bf16: dual_newton_covariance with the M x M x N product from
+    split-BF16 operands, as the covariance of a Newton step.  With Y' = yT - centre (the device's centre: YTilde), w the
+    point's weights and bf(v) = round-to-nearest-even of (float)v to bfloat16 (forces._bf16_split):
+
+      a = Y'_ij (FP64)         a_hi = bf(a),  a_lo = bf((float)a - a_hi)
+      t = a w_j (FP64)         t_hi = bf(t),  t_lo = bf((float)t - t_hi)
+      G' = sum_j (a_hi t_hi + a_hi t_lo + a_lo t_hi)            each product exact in FP64, summed in FP64
+      C~ = G' - ybar' ybar'^T,  ybar' = ybar - centre           FP64
+
+    The lower triangle is computed and mirrored: symmetric bit for bit."""
+    from .forces import _bf16_split
+    a = yT - np.asarray(centre, dtype=np.float64).reshape(-1)[:, None]
+    a_hi, a_lo = _bf16_split(a)
+    t_hi, t_lo = _bf16_split(a * p["w"][None, :])
+    yc = p["ybar"] - np.asarray(centre, dtype=np.float64).reshape(-1)
+    C = a_hi.dot(t_hi.T) + a_hi.dot(t_lo.T) + a_lo.dot(t_hi.T) - np.outer(yc, yc)
+    return np.tril(C) + np.tril(C, -1).T
+
+
+def dual_newton_step(p, yT, theta, C=None):
+    """(u, z) at a point of _dual_newton_point: one covariance (C: from another source than dual_newton_covariance; only
+    the step's quality depends on it), one Cholesky factorisation of C + theta I (SPD for every theta > 0), one centred
+    forward pass on grad, one centred adjoint pass on r + z"""
     import scipy.linalg
     Yc = yT - p["ybar"][:, None]
-    C = (Yc * p["w"]).dot(Yc.T)
+    if C is None:
+        C = (Yc * p["w"]).dot(Yc.T)
     b = Yc.dot(p["grad"])
     L = np.linalg.cholesky(C + theta * np.eye(C.shape[0]))
     z = -scipy.linalg.cho_solve((L, True), b)
@@ -211,8 +233,29 @@ def dual_newton_step(p, yT, theta):
     return u, z
 
 
-def dual_newton_bioen_log_posterior_base(gInit, G, yTilde, YTilde, theta, params):
-    """The numpy statement of the dual Newton minimizer of the log-weights objective.
+_DUAL_NEWTON_SOURCES = ("gram", "gram_bf16")
+
+
+def _dual_newton_source(params):
+    """the dual_newton parameter `hessian`, checked: -> "gram" | "gram_bf16" """
+    source = str(dict(params).get("hessian", "gram")).lower()
+    if source not in _DUAL_NEWTON_SOURCES:
+        raise RuntimeError("dual_newton:hessian=" + source + " not recognized (valid values = 'gram', 'gram_bf16')")
+    return source
+
+
+def _dual_newton_series_mode(params):
+    """the dual_newton parameter `series`, checked: -> warm (True) | cold (False)"""
+    mode = str(dict(params).get("series", "warm")).lower()
+    if mode not in ("warm", "cold"):
+        raise RuntimeError("dual_newton:series=" + mode + " not recognized (valid values = 'warm', 'cold')")
+    return mode == "warm"
+
+
+def dual_newton_bioen_log_posterior_base(gInit, G, yTilde, YTilde, theta, params, cov=None):
+    """The numpy statement of the dual Newton minimizer of the log-weights objective, the specification
+    of the device loop.  The covariance of the step comes from `params["hessian"]`: "gram" (dual_newton_covariance, the
+    default) or "gram_bf16" (dual_newton_covariance_bf16); `cov`, a dict source -> function(p, yT, centre), replaces them.
 
       1. stop: max|grad| <= gtol max w (the weight gate is relative to max w, so the test is) AND max|gamma| <= theta,
          grad = w gamma -> status 0.  The second half is the globalisation: where a step of size ~ 1 / theta has
@@ -224,12 +267,18 @@ def dual_newton_bioen_log_posterior_base(gInit, G, yTilde, YTilde, theta, params
       4. alpha = 1, 1/2, ...: f+ at g + alpha u; accept if f+ is finite and f+ - f <= 1e-4 alpha slope; at the rounding
          floor (|alpha slope| <= 8 eps |f|: f cannot judge the step) accept on max|grad+| < max|grad| instead, and a
          rejection there ends the run: status 2.  max_halvings rejections elsewhere: status 3.
+      5. rejected at the floor with "gram_bf16": the run goes over to "gram" (once, for the rest of this theta): the kept
+         point is evaluated again (one evaluation), then to 1 -- C anew, a new step.  Gradient, stop test and Armijo test
+         are FP64 whatever the source: only the step's quality depends on C, the optimum does not move.
 
-    -> dict(g, fmin, status, iterations, evaluations, factorisations, gmax, wmax).  theta <= 0 is refused: the step
-    divides by theta."""
+    -> dict(g, fmin, status, iterations, evaluations, factorisations, gmax, wmax, bf16_passes, switched).  theta <= 0 is
+    refused: the step divides by theta."""
     theta = float(theta)
     if not theta > 0.0:
         raise RuntimeError("dual_newton needs theta > 0 (the step divides by theta), got %r" % theta)
+    source = _dual_newton_source(params)
+    sources = dict(dict(gram=lambda p, yT, centre: dual_newton_covariance(p, yT), gram_bf16=dual_newton_covariance_bf16),
+                   **(cov or {}))
     c_ = dict(_DUAL_NEWTON_CONSTANTS, **{k: v for k, v in dict(params).items() if k in _DUAL_NEWTON_CONSTANTS})
     gtol, maxit = float(params.get("gtol", 1e-6)), int(params.get("max_iterations", 200))
     yT = np.asarray(yTilde, dtype=np.float64)
@@ -238,8 +287,8 @@ def dual_newton_bioen_log_posterior_base(gInit, G, yTilde, YTilde, theta, params
     logs0 = float(np.log(np.exp(Gv - Gv.max()).sum()) + Gv.max())
     eps = np.finfo(np.float64).eps
     p = _dual_newton_point(np.asarray(gInit, dtype=np.float64).reshape(-1).copy(), Gv, yT, YT, theta, logs0)
-    count = dict(iterations=0, evaluations=1, factorisations=0)
-    status = None
+    count = dict(iterations=0, evaluations=1, factorisations=0, bf16_passes=0)
+    status, switched = None, False
     while status is None:
         gmax, wmax = float(np.abs(p["grad"]).max()), float(p["w"].max())
         if gmax <= gtol * wmax and float(np.abs(p["gamma"]).max()) <= theta:
@@ -248,10 +297,11 @@ def dual_newton_bioen_log_posterior_base(gInit, G, yTilde, YTilde, theta, params
         if count["iterations"] >= maxit:
             status = 1
             break
-        u, _ = dual_newton_step(p, yT, theta)
+        u, _ = dual_newton_step(p, yT, theta, C=sources[source](p, yT, YT))
         count["factorisations"] += 1
+        count["bf16_passes"] += source == "gram_bf16"
         slope = float(p["grad"].dot(u))
-        alpha, trial = 1.0, None
+        alpha, trial, go_over = 1.0, None, False
         for _ in range(int(c_["max_halvings"])):
             q = _dual_newton_point(p["g"] + alpha * u, Gv, yT, YT, theta, logs0)
             count["evaluations"] += 1
@@ -259,6 +309,8 @@ def dual_newton_bioen_log_posterior_base(gInit, G, yTilde, YTilde, theta, params
             if floor:
                 if np.isfinite(q["f"]) and float(np.abs(q["grad"]).max()) < gmax:
                     trial = q
+                elif source == "gram_bf16":
+                    go_over = True
                 else:
                     status = 2
                 break
@@ -266,13 +318,33 @@ def dual_newton_bioen_log_posterior_base(gInit, G, yTilde, YTilde, theta, params
                 trial = q
                 break
             alpha *= 0.5
+        if go_over:
+            source, switched = "gram", True
+            count["evaluations"] += 1               # the device evaluates the kept point again: the slot held the trial
+            continue
         if trial is None:
             status = status or 3
             break
         p = trial
         count["iterations"] += 1
     return dict(count, g=p["g"], fmin=p["f"], status=status, gmax=float(np.abs(p["grad"]).max()),
-                wmax=float(p["w"].max()))
+                wmax=float(p["w"].max()), switched=switched)
+
+
+def dual_newton_series_base(gInit, G, yTilde, YTilde, thetas, params, warm=True):
+    """The numpy statement of Context.opt_dual_newton_logw_series: dual_newton_bioen_log_posterior_base for
+    the thetas in the order given; warm: theta k starts at the g theta k - 1 returned -- whatever its status --, else every
+    theta at gInit.  -> the list of its dicts; a status != 0 does not stop the series."""
+    thetas = [float(t) for t in thetas]
+    if not thetas or not all(t > 0.0 and np.isfinite(t) for t in thetas):
+        raise RuntimeError("dual_newton needs at least one theta, every theta > 0 and finite, got %r" % (thetas,))
+    g = np.asarray(gInit, dtype=np.float64).reshape(-1)
+    out = []
+    for t in thetas:
+        out.append(dual_newton_bioen_log_posterior_base(g, G, yTilde, YTilde, t, params))
+        if warm:
+            g = out[-1]["g"]
+    return out
 
 
 def _dual_newton_finish(who, res):
@@ -439,9 +511,11 @@ def find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg):
     if str(cfg["minimizer"]).upper() not in ('LIBLBFGS', 'LBFGS', 'GSL', 'SCIPY', 'DUAL_NEWTON'):      # rejected before anything touches the device
         raise RuntimeError("Library " + cfg["minimizer"] +
                            " not recognized (valid values =  'LIBLBFGS', 'GSL', 'scipy', 'scipy', 'dual_newton' ) ")
-    if str(cfg["minimizer"]).upper() == 'DUAL_NEWTON' and not float(theta) > 0.0:
-        raise RuntimeError("dual_newton needs theta > 0 (the step divides by theta), got %r" % float(theta))
-    _bfgs_on_device(cfg)                                 # refused combinations raise here, before the device is touched
+    if str(cfg["minimizer"]).upper() == 'DUAL_NEWTON':
+        if not float(theta) > 0.0:
+            raise RuntimeError("dual_newton needs theta > 0 (the step divides by theta), got %r" % float(theta))
+        _dual_newton_source(cfg["params"])
+    _bfgs_on_device(cfg)                               # refused combinations raise here, before the device is touched
     if _uses_device(cfg):
         with c_bioen.hold(yTilde, YTilde):
             return _find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg)
@@ -527,14 +601,50 @@ def _find_optimum(GInit, G, y, yTilde, YTilde, theta, cfg):
     return wopt, yopt, gopt, fmin_initial, fmin_final
 
 
+def _find_optimum_series_dual_newton(GInit, G, y, yTilde, YTilde, thetas, cfg):
+    """find_optimum_series with the dual_newton minimizer: on the device one call for the series (the matrix held once),
+    with use_c_functions false dual_newton_series_base on the numpy objective"""
+    thetas = [float(t) for t in thetas]
+    if not thetas or not all(t > 0.0 and np.isfinite(t) for t in thetas):       # refused before anything touches the device
+        raise RuntimeError("dual_newton needs at least one theta, every theta > 0 (the step divides by theta), got %r" % (thetas,))
+    _dual_newton_source(cfg["params"])
+    warm = _dual_newton_series_mode(cfg["params"])
+    g = GInit.copy()
+    gPrime = np.asarray(g[:].T)[0]
+
+    def finish(f0, gopts, fmins, ave):
+        out = []
+        for k in range(len(thetas)):
+            wopt = getWOpt(G, gopts[k])
+            out.append((wopt, ave(wopt), gopts[k], f0[k], fmins[k]))
+        return out
+
+    if not _uses_device(cfg):
+        f0 = [bioen_log_posterior_base(gPrime, g, G, yTilde, YTilde, t) for t in thetas]
+        res = dual_newton_series_base(gPrime, G, yTilde, YTilde, thetas, cfg["params"], warm=warm)
+        for t, r in zip(thetas, res):
+            _dual_newton_finish("dual_newton_series_base: theta = %r" % t, r)
+        return finish(f0, [r["g"] for r in res], [r["fmin"] for r in res], lambda w: common.getAve(w, y))
+    with c_bioen.hold(yTilde, YTilde):                 # one device copy for the whole series: at most one upload
+        f0 = [c_bioen.bioen_log_posterior_logw(gPrime, g, G, yTilde, YTilde, t) for t in thetas]
+        gopts, fmins = c_bioen.bioen_opt_dual_newton_logw_series(gPrime, G, yTilde, YTilde, thetas, cfg)
+        return finish(f0, gopts, fmins,
+                      lambda w: c_bioen.get_ave(w, yTilde, YTilde) if y is yTilde else common.getAve(w, y))
+
+
 def find_optimum_series(GInit, G, y, yTilde, YTilde, thetas, cfg):
-    """Not in the reference: ``find_optimum`` for a whole cold-started theta series in one device call
-    (what bioen/analyze/procedure.py:62-67 does one theta at a time).  Minimizer "lbfgs"/"liblbfgs"
-    only; every entry of the returned list is the 5-tuple ``find_optimum`` returns for that theta --
-    the optimisation itself bit for bit, since a batched run equals the single runs."""
+    """Not in the reference: ``find_optimum`` for a whole theta series in one device call
+    (what bioen/analyze/procedure.py:62-67 does one theta at a time).  Minimizer "lbfgs"/"liblbfgs": cold-started,
+    the optimisation itself bit for bit the single runs, since a batched run equals them.  Minimizer "dual_newton"
+    (DESIGN 6k): the thetas in the order given, theta k warm-started at theta k - 1's optimum -- or every theta from GInit
+    with ``dual_newton:series=cold`` --, the covariance of the steps from ``dual_newton:hessian``; a theta whose status is
+    not 0 raises, as ``find_optimum`` does.  Every entry of the returned list is the 5-tuple ``find_optimum`` returns
+    for that theta."""
     check_params_logweights(GInit, G, y, yTilde, YTilde)
+    if cfg["minimizer"].upper() == 'DUAL_NEWTON':
+        return _find_optimum_series_dual_newton(GInit, G, y, yTilde, YTilde, thetas, cfg)
     if cfg["minimizer"].upper() not in ('LIBLBFGS', 'LBFGS'):
-        raise RuntimeError("find_optimum_series needs the lbfgs minimizer, got " + str(cfg["minimizer"]))
+        raise RuntimeError("find_optimum_series needs the lbfgs or the dual_newton minimizer, got " + str(cfg["minimizer"]))
     g = GInit.copy()
     gPrime = np.asarray(g[:].T)[0]
     with c_bioen.hold(yTilde, YTilde):                 # one device copy for the whole series: at most one upload

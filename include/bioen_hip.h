@@ -739,6 +739,38 @@ typedef struct {
 int bioen_logwn_opt(bioen_hip_ctx* ctx, const double* g0, const double* G, double theta, const bioen_logwn_config* config,
                     double* gopt, bioen_logwn_result* result);
 
+/* ---- the theta series by dual Newton, and the covariance from split-BF16 operands.  DESIGN section 6k.  The refusals
+ * (BIOEN_HIP_ESTATE) are the two entries' above. ---- */
+
+/* bioen_logwn_cov's contract (arguments, point, buffer), C from the split-BF16 pass: the M x M x N product of operands split
+ * hi + lo into bfloat16, hi hi + hi lo + lo hi on the BF16 matrix cores with float accumulators, the sets added in double.
+ * |C_bf16 - C|_ik stays below 3 * 2^-16 sqrt(G'_ii G'_kk), G' the uncentred second moment: good for a Newton step, which
+ * is what it is for.  f and grad are bioen_logwn_cov's bits; bitwise symmetric; the same bits call after call. */
+int bioen_logwn_cov_bf16(bioen_hip_ctx* ctx, const double* g, const double* G, double theta, double* C, double* f, double* grad);
+
+typedef struct {
+    double fmin, gmax, wmax;        /* as in bioen_logwn_result */
+    int status, iterations, evaluations, factorisations;
+    int bf16_passes;                /* covariances formed by the split-BF16 pass (factorisations - bf16_passes: by the FP64 one) */
+    int switched;                   /* 1: a step from a split-BF16 covariance was rejected at the rounding floor of f and the
+                                       run went over to the FP64 pass for the rest of this theta (one more evaluation) */
+} bioen_logwn_series_result;
+
+/* The dual Newton minimizer for ntheta values of theta, in the order given, in one call: G goes up once, every N-vector
+ * stays in device memory between the thetas, n doubles come down per theta (gopt: [ntheta][n], results: [ntheta]).
+ *   source  0: the covariance of every step from the FP64 pass; 1: from the split-BF16 pass (bioen_logwn_cov_bf16's), with
+ *           the switch above.  Gradient, stop test and Armijo test are FP64 either way: the optimum is the same.
+ *   warm    1: theta k starts at the point theta k - 1 returned (theta 0 at g0); 0: every theta starts at g0.
+ * With source 0 a warm series is, bit for bit and count for count, ntheta chained bioen_logwn_opt calls each starting at
+ * the previous gopt; a cold one the ntheta single calls from g0.  A theta that ends with status != 0 does not stop the
+ * series: every status is reported, and with warm = 1 the next theta starts from that theta's kept point.
+ * BIOEN_HIP_EINVAL, before the device, the point or a session are touched, on NULL arguments, ntheta < 1, any theta <= 0 or
+ * not finite, source or warm out of range, and a config bioen_logwn_opt refuses.  Returns 0 with every status; the last
+ * theta's returned point is then the context's kept log-weights point.  Ends a BFGS session. */
+int bioen_logwn_series(bioen_hip_ctx* ctx, const double* g0, const double* G, const double* thetas, int ntheta,
+                       const bioen_logwn_config* config, int source, int warm, double* gopt,
+                       bioen_logwn_series_result* results);
+
 #ifdef __cplusplus
 }
 #endif
