@@ -1,7 +1,7 @@
 // The dense Hessian and the covariance of the forces objective in one pass (part of api.hip's translation unit: uses its
 // static helpers), from FP64 operands -- bioen_hip_forces_gram; kernels: kernels_forces_gram.hip; DESIGN section 6e -- or
 // from split-BF16 operands on the BF16 matrix cores, for a Newton minimizer -- bioen_hip_forces_gram_bf16; kernel:
-// kernels_forces_gram_bf16.hip; DESIGN section 6g.  Two entries, not two modes of one: each pass has a buffer of its own,
+// k_forces_gram_bf16, in the same file; DESIGN section 6g.  Two entries, not two modes of one: each pass has a buffer of its own,
 // so that bioen_hip_forces_gram's results stay bitwise what they are.  Everything else is one function, fgram_entry; the
 // point, the guard and the buffers are api_forces_point.inl's.
 
@@ -20,7 +20,7 @@ static int fgram_compute(bioen_hip_ctx* c, int source, const double** cov, const
     if ((rc = ensure_scratch(c, which, p.doubles))) return rc;
     double* buf = c->scratch[which].p;
     const ProblemSlot& s0 = c->slot[0];
-    (source ? launch_forces_gram_bf16 : launch_forces_gram)(c, p, buf, s0.a, s0.scal, c->fpoint_q, c->fpoint_ybar, c->point_theta);
+    launch_forces_gram(c, p, buf, s0.a, s0.scal, c->fpoint_q, c->fpoint_ybar, c->point_theta, source != 0);
     if ((rc = check_launch())) return rc;
     if (!source) c->fgram_fresh = 1;                          // (bioen_laplace_forces at the same kept point takes them as they stand)
     if (cov) *cov = buf + p.cov_at;

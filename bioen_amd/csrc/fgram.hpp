@@ -1,10 +1,11 @@
-// What the dense Gram passes share (kernels_forces_gram.hip, kernels_forces_gram_bf16.hip, kernels_logw_newton.hip; DESIGN
-// 6e, 6g, 6j): their arguments, the layout of what a set leaves, and everything a wave does that is not arithmetic -- which
-// (set, sub-tile) it owns, its rows' centres, the matrix half of a strip's fetch, the row sums on their way out.
-// The FP64 pass itself is here too, once (fgram_pass): k_forces_gram and k_logw_gram are its two instances, each with a
-// POINT that says how many matrices a wave accumulates and how a column's weights come from what the point keeps.  The
-// BF16 kernels keep loops of their own: their weights arrive by shuffles and their operands are split (the split and the
-// instruction are here, once; one templated loop for both did not leave k_forces_gram_bf16's code object as it was: DESIGN 6k).
+// The dense Gram passes (kernels_forces_gram.hip, kernels_logw_newton.hip): their arguments, the
+// layout of what a set leaves, and everything a wave does that is not arithmetic -- which (set, sub-tile) it owns, its rows'
+// centres, the matrix half of a strip's fetch, the row sums on their way out.  The passes themselves are here too, each
+// once: the FP64 pass (fgram_pass: k_forces_gram and k_logw_gram are its two instances) and the split-BF16 pass
+// (fgram16_pass: k_forces_gram_bf16 and k_logw_gram_bf16), each instance with a POINT that says how many matrices a wave
+// accumulates and how a column's weights come from what the point keeps.  The two methods' points are here as well, each
+// once for both precisions: the FP64 pass forms the weights of four columns per lane, the BF16 pass those of one, handed
+// round by shuffles.
 #pragma once
 
 #include "strip.hpp"
@@ -128,7 +129,67 @@ __device__ __forceinline__ void fgram_store_row_sums(const FGramArgs& q, const F
     }
 }
 
-// ---- the split-BF16 passes' operands (k_forces_gram_bf16, k_logw_gram_bf16) ------------------------------------
+// ---- the two methods' points ----------------------------------------------------------------------------------------------
+// A Point<kCols> holds what the point keeps for kCols of a strip's columns (col, col + 4, ...) and supplies
+//   static double scalar(q, w)                 the wave's scalar of the point
+//   void load(q, col)                          its registers from the point's vectors
+//   void weights(scalar, k, valid, u1, u2)     the two weights of its column k; `valid`: the column lies below n
+// Matrix 0 of a pass is weighted by u1, matrix 1 (kMats = 2) by u2; the row sums of Y' u2 ride along, and with kSumU2
+// sum u2 itself.  The FP64 pass takes four columns per lane (4 qq + (lane >> 4)), the BF16 pass one (lane & 15).
+
+// The forces point: the weights as the SM_PRODUCT form of the strip kernels makes them, u1 = w0 exp(x' - log s), u2 = u1
+// (q - qbar); columns beyond n weigh nothing (the padding of x' is zero: the exponential there is finite)
+template <int kCols>
+struct ForcesGramPoint {
+    static constexpr int kMats = 2;
+    static constexpr bool kSumU2 = false;
+    double w0[kCols], x[kCols], qv[kCols];
+    __device__ __forceinline__ static double scalar(const FGramArgs& q, const FGramWave&) { return q.pscal[S_LOGS]; }
+    __device__ __forceinline__ void load(const FGramArgs& q, size_t col) {
+#pragma unroll
+        for (int k = 0; k < kCols; ++k) {
+            w0[k] = q.w0[col + 4 * k];
+            x[k] = q.x[col + 4 * k];
+            qv[k] = q.qv[col + 4 * k];
+        }
+    }
+    __device__ __forceinline__ void weights(double logs, int k, bool valid, double& u1, double& u2) const {
+        const double e = exp(x[k] - logs);
+        u1 = valid ? w0[k] * e : 0.0;
+        u2 = u1 * qv[k];
+    }
+};
+
+// The log-weights point, in FGramArgs x = e, qv = grad, pscal = the point's scalar slot, w0 unread: the weights are slot 0's
+// e times the softmax factor of the set's segment (S_INV), u2 = grad; columns beyond n weigh nothing
+template <int kCols>
+struct LogwGramPoint {
+    static constexpr int kMats = 1;
+    static constexpr bool kSumU2 = true;
+    double e[kCols], gr[kCols];
+    __device__ __forceinline__ static double scalar(const FGramArgs& q, const FGramWave& w) { return q.pscal[S_INV + w.v]; }
+    __device__ __forceinline__ void load(const FGramArgs& q, size_t col) {
+#pragma unroll
+        for (int k = 0; k < kCols; ++k) {
+            e[k] = q.x[col + 4 * k];
+            gr[k] = q.qv[col + 4 * k];
+        }
+    }
+    __device__ __forceinline__ void weights(double inv, int k, bool valid, double& u1, double& u2) const {
+        u1 = valid ? e[k] * inv : 0.0;
+        u2 = valid ? gr[k] : 0.0;
+    }
+};
+
+// a strip's registers: the chunks of the wave's two slices and the point's columns
+template <class Point>
+struct FGramRegs {
+    d2 a[kWaveRows / 8];
+    d2 b[kWaveRows / 8];
+    Point pt;
+};
+
+// ---- the split-BF16 pass's operands -----------------------------------------------------------------------
 typedef float fl4 __attribute__((ext_vector_type(4)));
 typedef short bh4 __attribute__((ext_vector_type(4)));      // four bfloat16: an operand fragment of the 16-deep instruction
 typedef unsigned u2v __attribute__((ext_vector_type(2)));   // the same two registers as they are filled: elements (0, 1) | (2, 3)
@@ -156,17 +217,7 @@ __device__ __forceinline__ fl4 mfma16(u2v a, u2v b, fl4 c) {
 // k = lane >> 4) -- as A for its own row block and, the same registers of another slice, as B: G'_IJ += Y'_I diag(u) Y'_J^T
 // with no transpose and no LDS image.  A wave owns a 64 x 64 sub-tile of Point::kMats matrices (16 accumulators of 4 doubles
 // each), matrix 0 weighted by u1, matrix 1 by u2; the row sums of Y' u2 ride along, and with Point::kSumU2 sum u2 itself.
-// A Point holds the strip's per-column registers (columns 4 qq + (lane >> 4), qq = 0 .. 3) and supplies
-//   static double scalar(q, w)                 the wave's scalar of the point
-//   void load(q, col)                          its registers from the point's vectors
-//   void weights(scalar, qq, valid, u1, u2)    a column's two weights; `valid`: the column lies below n
-template <class Point>
-struct FGramRegs {
-    d2 a[kWaveRows / 8];
-    d2 b[kWaveRows / 8];
-    Point pt;
-};
-
+// Point: a four-column point, the strip's columns 4 qq + (lane >> 4), qq = 0 .. 3.
 template <class Point>
 __device__ __forceinline__ void fgram_pass(const FGramArgs& q) {
     constexpr int kMats = Point::kMats;
@@ -257,6 +308,126 @@ __device__ __forceinline__ void fgram_pass(const FGramArgs& q) {
     fgram_store_row_sums(q, w, lq, lr, rs);
     if constexpr (Point::kSumU2)
         if (w.si == 0) {                            // (sj = 0 too) over the set's columns: the four quarters hold four columns each
+            const double t = quad_sum(sg);
+            if (lane == 0) set[q.rows_at + (size_t)q.nsl * kWaveRows] = t;
+        }
+}
+
+// ---- the split-BF16 pass ------------------------------------------------------------------------------------
+// fgram_pass with the M x M x N products from SPLIT-BF16 operands on the BF16 matrix cores; the sets, their order and the
+// layout of what a set leaves are fgram_pass's:
+//   a = Y_ij - centre_i (FP64)        a_hi = bf(a),  a_lo = bf((float)a - a_hi)          bf: float, then bfloat16, both
+//   t = a u_j           (FP64)        t_hi = bf(t),  t_lo = bf((float)t - t_hi)              round-to-nearest-even
+//   G'[u]_ik = sum_j (a_hi t_hi + a_hi t_lo + a_lo t_hi)        v_mfma_f32_16x16x16_bf16, f32 accumulators
+// The row sums of Y' u2 (and sum u2) stay fgram_pass's FP64 fma chains in its column order (they feed cancellations): the
+// same bits.  The strip copy's registers (row = lane & 15, the strip's columns 4 qq + (lane >> 4) in qq = 0 .. 3) are a
+// 16-row, 16-deep BF16 operand as they stand: element qq of a lane's fragment is depth index 4 (lane >> 4) + qq of the
+// instruction, for the A and the B operand alike, so the instruction contracts over the strip's 16 columns in a permuted
+// order.  A wave owns a 64 x 64 sub-tile of Point::kMats matrices (16 accumulators of 4 floats each).  A set's f32 sums
+// leave as doubles on fgram_elem's layout, so k_fgram_sum_sets adds the sets IN FP64 in its fixed order and the FP64 pass's
+// finishing kernels take them as they are.
+// Point: a one-column point, the strip's column lane & 15 -- a lane forms the weights of ONE column with the operations of
+// the four-column point (the same bits), the lanes that multiply with them receive them by shuffles.
+template <class Point>
+__device__ __forceinline__ void fgram16_pass(const FGramArgs& q) {
+    constexpr int kMats = Point::kMats;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lq = lane >> 4, lr = lane & 15;
+    FGramWave w;
+    if (!fgram_decode(q, lane, wave, w)) return;
+    const double scal = Point::scalar(q, w);
+    double ca[4], cb[4];                            // the centres of the lane's rows
+    fgram_centres(q, w, lr, ca, cb);
+
+    auto fetch = [&](int i, FGramRegs<Point>& r) {
+        const int s = fgram_strip(q, w, i);
+        fgram_fetch(q, w, s, r.a, r.b);
+        r.pt.load(q, (size_t)s * kStripCols + lr);
+    };
+
+    fl4 acc[kMats][4][4];                           // [matrix][row block of slice si][row block of slice sj]
+    double rs[4], sg = 0.0;                         // the lane's share of the row sums of Y' u2 (slice si), of sum u2
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        rs[h] = 0.0;
+#pragma unroll
+        for (int gb = 0; gb < 4; ++gb)
+#pragma unroll
+            for (int mat = 0; mat < kMats; ++mat) acc[mat][h][gb] = fl4{0.f, 0.f, 0.f, 0.f};
+    }
+
+    // One register set, as in fgram_pass: a strip's operands are centred, weighted and split into registers of their own
+    // as soon as it has arrived, the set is refilled with the NEXT strip, which travels while this one is multiplied.
+    FGramRegs<Point> pre;
+    fetch(0, pre);
+#pragma unroll 1
+    for (int i = 0; i < w.tg; ++i) {
+        // formed once per column (lane & 15) and handed to the lanes that multiply with them: lane 4 qq + lq formed column
+        // 4 qq + lq -- fgram_pass's columns and order
+        const size_t colc = (size_t)fgram_strip(q, w, i) * kStripCols + lr;
+        double uc[2], u[2][4];                      // [u1 | u2]
+        pre.pt.weights(scal, 0, colc < (size_t)q.n, uc[0], uc[1]);
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) {
+            u[0][qq] = __shfl(uc[0], 4 * qq + lq, 64);
+            u[1][qq] = __shfl(uc[1], 4 * qq + lq, 64);
+            if constexpr (Point::kSumU2) sg += u[1][qq];
+        }
+        u2v ah[4], al[4], bh[kMats][4], bl[kMats][4];           // [row block]: the fragments, element qq = column quad qq
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+#pragma unroll
+            for (int qp = 0; qp < 2; ++qp) {                    // the column quads 2 qp (.x) and 2 qp + 1 (.y)
+                const d2 av = pre.a[2 * h + qp], bv = pre.b[2 * h + qp];
+                const double a0 = av.x - ca[h], a1 = av.y - ca[h];
+                const double b0 = bv.x - cb[h], b1 = bv.y - cb[h];
+                rs[h] = fma(a0, u[1][2 * qp], rs[h]);
+                rs[h] = fma(a1, u[1][2 * qp + 1], rs[h]);
+                unsigned hi, lo;
+                bf_split2(a0, a1, hi, lo);
+                ah[h][qp] = hi;
+                al[h][qp] = lo;
+#pragma unroll
+                for (int mat = 0; mat < kMats; ++mat) {
+                    bf_split2(b0 * u[mat][2 * qp], b1 * u[mat][2 * qp + 1], hi, lo);
+                    bh[mat][h][qp] = hi;
+                    bl[mat][h][qp] = lo;
+                }
+            }
+        fetch(i + 1 < w.tg ? i + 1 : i, pre);       // unconditional
+        asm volatile("" ::: "memory");              // the loads are issued HERE, in front of the products
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+#pragma unroll
+            for (int gb = 0; gb < 4; ++gb) {        // hi hi, hi lo, lo hi: the matrices alternate inside each group
+#pragma unroll
+                for (int mat = 0; mat < kMats; ++mat) acc[mat][h][gb] = mfma16(ah[h], bh[mat][gb], acc[mat][h][gb]);
+#pragma unroll
+                for (int mat = 0; mat < kMats; ++mat) acc[mat][h][gb] = mfma16(ah[h], bl[mat][gb], acc[mat][h][gb]);
+#pragma unroll
+                for (int mat = 0; mat < kMats; ++mat) acc[mat][h][gb] = mfma16(al[h], bh[mat][gb], acc[mat][h][gb]);
+            }
+    }
+
+    // The set leaves as doubles on fgram_pass's layout (fgram_elem: element (i, j) of a 16 x 16 block at register
+    // (i & 15) >> 2 of lane 16 (i & 3) + j).  Result register r of lane 16 lq + lr of THIS instruction is row 4 lq + r,
+    // column lr of the block: it goes to register slot lq, lane 16 r + lr.  Row blocks beyond the strip's last one were
+    // redirected (strip_chunk_offsets): what they leave lies beyond row m and is never read.
+    double* const set = q.partial + (size_t)w.set * q.set_stride;
+    double* const dst = set + (size_t)fgram_sub(w.si, w.sj) * fgram_sub_doubles(kMats) + lr;
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+        for (int gb = 0; gb < 4; ++gb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int mat = 0; mat < kMats; ++mat)
+                    dst[((mat * 16 + h * 4 + gb) * 4 + lq) * 64 + 16 * r] = (double)acc[mat][h][gb][r];
+    fgram_store_row_sums(q, w, lq, lr, rs);
+    if constexpr (Point::kSumU2)
+        if (w.si == 0) {                            // (sj = 0 too) as fgram_pass leaves it
             const double t = quad_sum(sg);
             if (lane == 0) set[q.rows_at + (size_t)q.nsl * kWaveRows] = t;
         }

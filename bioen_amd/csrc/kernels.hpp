@@ -187,8 +187,8 @@ void launch_forces_hp_tangent(bioen_hip_ctx* c, const struct ForcesRound& fr);  
 void launch_forces_hp_product(bioen_hip_ctx* c, const struct ForcesRound& fr);         // [matrix pass 2]
 void launch_forces_colsum(bioen_hip_ctx* c, const double* u_c, double* out);           // out = Y'^T u on the forces passes' copy
 
-// ---- dense Hessian and covariance of the forces objective in one pass (kernels_forces_gram.hip; what its
-// kernel shares with the BF16 pass's: fgram.hpp) ---------------------------------------------------------------------------
+// ---- dense Hessian and covariance of the forces objective in one pass (kernels_forces_gram.hip; the FP64
+// and the split-BF16 pass themselves: fgram.hpp) ---------------------------------------------------------------------------
 struct GramPlan {                   // the sets of a dense Gram pass and what lies behind them, both methods' 
     int nsl, ntiles, nsub;          // 64-row slices, 128-row tile pairs I >= J, 64 x 64 sub-tiles of the lower triangle
     int gs, nsets;                  // groups per canonical segment; sets of this context (local segments x gs)
@@ -199,8 +199,10 @@ struct GramPlan {                   // the sets of a dense Gram pass and what li
 // mats: matrices per sub-tile; set_extra: doubles of a set behind its row sums; tail: doubles behind C
 GramPlan gram_plan(const bioen_hip_ctx* c, int mats, int set_extra, size_t tail);
 GramPlan forces_gram_plan(const bioen_hip_ctx* c);
+// bf16: the sets from k_forces_gram_bf16 (split-BF16 operands on the BF16 matrix cores) into buf, a buffer of that
+// pass's own; the plan, the sets' layout and the tail are the same
 void launch_forces_gram(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* x, const double* pscal,
-                        const double* qv, const double* ybar, double theta);
+                        const double* qv, const double* ybar, double theta, bool bf16);
 // what follows the sets, whichever kernel has written them: their sum in its fixed order, the rank corrections, + C C
 // (k_fgram_sum_sets, k_fgram_finish, k_fgram_square, defined in kernels_forces_gram.hip)
 void launch_fgram_tail(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* ybar, double theta);
@@ -224,11 +226,6 @@ void launch_logwn_stats(bioen_hip_ctx* c, const double* x, const double* e, cons
 // u = -[(x - G - P) + cadj / theta] (the padding zero); out[LN_SLOPE] <- grad . u
 void launch_logwn_step(bioen_hip_ctx* c, const double* x, const double* cadj, const double* grad, const double* pscal,
                        double theta, double* u, double* out);
-
-// the same pass with split-BF16 operands on the BF16 matrix cores (kernels_forces_gram_bf16.hip): the plan, the
-// sets' layout and the tail are the FP64 pass's, buf is a buffer of its own
-void launch_forces_gram_bf16(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* x, const double* pscal,
-                             const double* qv, const double* ybar, double theta);
 
 // ---- dense FP64 Cholesky factorisation and solves on the device, M <= 1024 (kernels_forces_newton.hip) --------
 constexpr int kFNewtonPanel = 64;           // columns of a panel: a diagonal tile is one wave's, a trailing tile four waves'

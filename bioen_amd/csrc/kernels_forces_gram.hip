@@ -15,35 +15,16 @@
 // (set, sub-tile) has exactly one writer; k_fgram_sum_sets adds the sets in the fixed order
 //   sum over segments (in index order) of [ the segment's groups added in turn ]
 // -- no floating-point atomics, and the shape of the sum is a function of (segcols, M) alone.
-// The arguments, a wave's decode, its centres, the matrix fetch and the row sums' way out are fgram.hpp's too: the BF16 pass
-// (kernels_forces_gram_bf16.hip) runs the same ones around a loop of its own.
+// k_forces_gram_bf16 is fgram.hpp's split-BF16 pass (fgram16_pass) at the same point: the Hessian for a Newton
+// minimizer, only the two M x M x N products in another precision -- the sets on the same layout, the row sums the same
+// bits, everything behind the sets shared (launch_fgram_tail).
 #include "fgram.hpp"
 
 namespace bioen {
 
-// The forces point: the weights as the SM_PRODUCT form of the strip kernels makes them, u1 = w0 exp(x' - log s), u2 = u1
-// (q - qbar); columns beyond n weigh nothing (the padding of x' is zero: the exponential there is finite)
-struct ForcesGramPoint {
-    static constexpr int kMats = 2;
-    static constexpr bool kSumU2 = false;
-    double w0[4], x[4], qv[4];
-    __device__ __forceinline__ static double scalar(const FGramArgs& q, const FGramWave&) { return q.pscal[S_LOGS]; }
-    __device__ __forceinline__ void load(const FGramArgs& q, size_t col) {
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-            w0[qq] = q.w0[col + 4 * qq];
-            x[qq] = q.x[col + 4 * qq];
-            qv[qq] = q.qv[col + 4 * qq];
-        }
-    }
-    __device__ __forceinline__ void weights(double logs, int qq, bool valid, double& u1, double& u2) const {
-        const double e = exp(x[qq] - logs);
-        u1 = valid ? w0[qq] * e : 0.0;
-        u2 = u1 * qv[qq];
-    }
-};
-
-__global__ __launch_bounds__(256, 1) void k_forces_gram(FGramArgs q) { fgram_pass<ForcesGramPoint>(q); }
+__global__ __launch_bounds__(256, 1) void k_forces_gram(FGramArgs q) { fgram_pass<ForcesGramPoint<4>>(q); }
+// (32 f32 accumulators of 4: 128 AGPRs; one wave per SIMD)
+__global__ __launch_bounds__(256, 1) void k_forces_gram_bf16(FGramArgs q) { fgram16_pass<ForcesGramPoint<1>>(q); }
 
 // out[e] = sum over segments (in index order) of [ the segment's gs sets added in turn ], e < count: on the sets' own
 // layout (coalesced); out is one more set behind the partials
@@ -147,9 +128,10 @@ void launch_fgram_tail(bioen_hip_ctx* c, const GramPlan& p, double* buf, const d
 }
 
 // buf: forces_gram_plan's doubles; x, pscal, qv, ybar: the kept point's.  Leaves C at buf + cov_at, H at buf + tail_at.
+// bf16: the sets from k_forces_gram_bf16 (C~, H~; buf a buffer of that pass's own), everything behind them unchanged
 void launch_forces_gram(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* x, const double* pscal,
-                        const double* qv, const double* ybar, double theta) {
-    hipLaunchKernelGGL(k_forces_gram, dim3(fgram_blocks(p)), dim3(256), 0, c->stream,
+                        const double* qv, const double* ybar, double theta, bool bf16) {
+    hipLaunchKernelGGL(bf16 ? k_forces_gram_bf16 : k_forces_gram, dim3(fgram_blocks(p)), dim3(256), 0, c->stream,
                        fgram_args(c, p, buf, x, pscal, qv));
     launch_fgram_tail(c, p, buf, ybar, theta);
 }

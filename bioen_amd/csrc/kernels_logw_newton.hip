@@ -10,8 +10,8 @@
 // accumulators (128 AGPRs + 224 VGPRs, no scratch; one wave per SIMD as there: with two, in 256 registers, the compiler
 // spills 23 of them).  A wave owns a 64 x 64 sub-tile; the row sums ride along with u = grad, and so does sum grad.  One
 // writer per (set, sub-tile), the sets added by k_fgram_sum_sets in its fixed order, C finished on the lower triangle and
-// mirrored: bitwise symmetric.  k_logw_gram_bf16 is the same pass with the product from split-BF16 operands on the
-// BF16 matrix cores, for the loop's step: the sets on the same layout, everything behind them shared, -b the same bits.
+// mirrored: bitwise symmetric.  k_logw_gram_bf16 is fgram.hpp's split-BF16 pass (fgram16_pass: k_forces_gram_bf16's)
+// at the same point, for the loop's step: the sets on the same layout, everything behind them shared, -b the same bits.
 // Around it the N-vector kernels of the loop, on the k_hessp_* pattern (kernels_hessp.hip): block partials into the X_GRAD
 // stage, met in segment order by a one-block kernel.  The entries that launch them serve unsharded contexts only: the
 // stage is not exchanged.
@@ -19,137 +19,11 @@
 
 namespace bioen {
 
-// The log-weights point, in FGramArgs x = e, qv = grad, pscal = the point's scalar slot, w0 unread: the weights are slot 0's
-// e times the softmax factor of the set's segment (S_INV), u2 = grad; columns beyond n weigh nothing
-struct LogwGramPoint {
-    static constexpr int kMats = 1;
-    static constexpr bool kSumU2 = true;
-    double e[4], gr[4];
-    __device__ __forceinline__ static double scalar(const FGramArgs& q, const FGramWave& w) { return q.pscal[S_INV + w.v]; }
-    __device__ __forceinline__ void load(const FGramArgs& q, size_t col) {
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-            e[qq] = q.x[col + 4 * qq];
-            gr[qq] = q.qv[col + 4 * qq];
-        }
-    }
-    __device__ __forceinline__ void weights(double inv, int qq, bool valid, double& u1, double& u2) const {
-        u1 = valid ? e[qq] * inv : 0.0;
-        u2 = valid ? gr[qq] : 0.0;
-    }
-};
-
-__global__ __launch_bounds__(256, 1) void k_logw_gram(FGramArgs q) { fgram_pass<LogwGramPoint>(q); }
-
-// k_logw_gram's pass with the M x M x N product from SPLIT-BF16 operands on the BF16 matrix cores, as k_forces_gram_bf16
-// (kernels_forces_gram_bf16.hip) forms its two -- the step's covariance for the dual Newton loop:
-//   a = Y'_ij - centre_i (FP64)       a_hi = bf(a),  a_lo = bf((float)a - a_hi)          bf: float, then bfloat16, both
-//   t = a u1_j           (FP64)       t_hi = bf(t),  t_lo = bf((float)t - t_hi)              round-to-nearest-even
-//   G'_ik = sum_j (a_hi t_hi + a_hi t_lo + a_lo t_hi)           v_mfma_f32_16x16x16_bf16, f32 accumulators
-// The point is LogwGramPoint's (u1 = e S_INV[segment], u2 = grad, columns beyond n weigh nothing), formed once per column
-// (lane & 15) and handed round by shuffles.  The row sums of Y' grad and sum grad stay FP64 fma chains, the operations of
-// fgram_pass<LogwGramPoint> in its order: -b keeps its bits.  The strip copy's registers are 16-deep BF16 fragments as they
-// stand (element qq of a lane's fragment is depth index 4 (lane >> 4) + qq, for A and B alike); a set's f32 sums leave as
-// doubles on fgram_elem's layout with one matrix, so k_fgram_sum_sets and k_lgram_finish take them as they are.
-struct LGram16Regs {
-    d2 a[kWaveRows / 8];
-    d2 b[kWaveRows / 8];
-    double e, gr;                    // the strip's column lane & 15
-};
+__global__ __launch_bounds__(256, 1) void k_logw_gram(FGramArgs q) { fgram_pass<LogwGramPoint<4>>(q); }
 
 // 16 f32 accumulators where k_forces_gram_bf16 has 32: 236 VGPRs, no AGPRs, no scratch -- two waves per SIMD (with bounds of
 // one wave the compiler takes 172 VGPRs + 64 AGPRs, runs two all the same, and is no faster: DESIGN 6k)
-__global__ __launch_bounds__(256, 2) void k_logw_gram_bf16(FGramArgs q) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lq = lane >> 4, lr = lane & 15;
-    FGramWave w;
-    if (!fgram_decode(q, lane, wave, w)) return;
-    const double inv = q.pscal[S_INV + w.v];
-    double ca[4], cb[4];                            // the centres of the lane's rows
-    fgram_centres(q, w, lr, ca, cb);
-
-    auto fetch = [&](int i, LGram16Regs& r) {
-        const int s = fgram_strip(q, w, i);
-        fgram_fetch(q, w, s, r.a, r.b);
-        const size_t col = (size_t)s * kStripCols + lr;
-        r.e = q.x[col];
-        r.gr = q.qv[col];
-    };
-
-    fl4 acc[4][4];                                  // [row block of slice si][row block of slice sj]
-    double rs[4], sg = 0.0;                         // the lane's share of the row sums of Y' grad (slice si), of sum grad
-#pragma unroll
-    for (int h = 0; h < 4; ++h) {
-        rs[h] = 0.0;
-#pragma unroll
-        for (int gb = 0; gb < 4; ++gb) acc[h][gb] = fl4{0.f, 0.f, 0.f, 0.f};
-    }
-
-    // One register set, as in fgram_pass: a strip's operands are centred, weighted and split into registers of their own
-    // as soon as it has arrived, the set is refilled with the NEXT strip, which travels while this one is multiplied.
-    LGram16Regs pre;
-    fetch(0, pre);
-#pragma unroll 1
-    for (int i = 0; i < w.tg; ++i) {
-        const size_t colc = (size_t)fgram_strip(q, w, i) * kStripCols + lr;
-        const bool valid = colc < (size_t)q.n;
-        const double u1c = valid ? pre.e * inv : 0.0;
-        const double u2c = valid ? pre.gr : 0.0;
-        double u1[4], u2[4];
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {            // lane 4 qq + lq formed column 4 qq + lq: fgram_pass's columns and order
-            u1[qq] = __shfl(u1c, 4 * qq + lq, 64);
-            u2[qq] = __shfl(u2c, 4 * qq + lq, 64);
-            sg += u2[qq];
-        }
-        u2v ah[4], al[4], bh[4], bl[4];             // [row block]: the fragments, element qq = column quad qq
-#pragma unroll
-        for (int h = 0; h < 4; ++h)
-#pragma unroll
-            for (int qp = 0; qp < 2; ++qp) {        // the column quads 2 qp (.x) and 2 qp + 1 (.y)
-                const d2 av = pre.a[2 * h + qp], bv = pre.b[2 * h + qp];
-                const double a0 = av.x - ca[h], a1 = av.y - ca[h];
-                const double b0 = bv.x - cb[h], b1 = bv.y - cb[h];
-                rs[h] = fma(a0, u2[2 * qp], rs[h]);
-                rs[h] = fma(a1, u2[2 * qp + 1], rs[h]);
-                unsigned hi, lo;
-                bf_split2(a0, a1, hi, lo);
-                ah[h][qp] = hi;
-                al[h][qp] = lo;
-                bf_split2(b0 * u1[2 * qp], b1 * u1[2 * qp + 1], hi, lo);
-                bh[h][qp] = hi;
-                bl[h][qp] = lo;
-            }
-        fetch(i + 1 < w.tg ? i + 1 : i, pre);       // unconditional
-        asm volatile("" ::: "memory");              // the loads are issued HERE, in front of the products
-#pragma unroll
-        for (int h = 0; h < 4; ++h)
-#pragma unroll
-            for (int gb = 0; gb < 4; ++gb) {
-                acc[h][gb] = mfma16(ah[h], bh[gb], acc[h][gb]);
-                acc[h][gb] = mfma16(ah[h], bl[gb], acc[h][gb]);
-                acc[h][gb] = mfma16(al[h], bh[gb], acc[h][gb]);
-            }
-    }
-
-    // The set leaves as doubles on fgram_elem's layout with one matrix.  Result register r of lane 16 lq + lr of THIS
-    // instruction is row 4 lq + r, column lr of the block: it goes to register slot lq, lane 16 r + lr.  Row blocks beyond
-    // the strip's last one were redirected (strip_chunk_offsets): what they leave lies beyond row m and is never read.
-    double* const set = q.partial + (size_t)w.set * q.set_stride;
-    double* const dst = set + (size_t)fgram_sub(w.si, w.sj) * fgram_sub_doubles(1) + lr;
-#pragma unroll
-    for (int h = 0; h < 4; ++h)
-#pragma unroll
-        for (int gb = 0; gb < 4; ++gb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dst[((h * 4 + gb) * 4 + lq) * 64 + 16 * r] = (double)acc[h][gb][r];
-    fgram_store_row_sums(q, w, lq, lr, rs);
-    if (w.si == 0) {                                // (sj = 0 too) sum grad over the set's columns, as fgram_pass leaves it
-        const double t = quad_sum(sg);
-        if (lane == 0) set[q.rows_at + (size_t)q.nsl * kWaveRows] = t;
-    }
-}
+__global__ __launch_bounds__(256, 2) void k_logw_gram_bf16(FGramArgs q) { fgram16_pass<LogwGramPoint<1>>(q); }
 
 // The rank correction and the affine model's scales on the lower triangle, mirrored; the blocks of tile column 0 also leave
 // -b for the solve.  16 x 16 threads per block, blocks above the diagonal leave.

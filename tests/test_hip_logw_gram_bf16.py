@@ -23,6 +23,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from test_hip_forces_gram import GATE as FORCES_GATE
 from test_hip_forces_hessp import estate, problem
 from test_hip_logw_dual_newton import SHAPES as COV_SHAPES, logw_problem
 from test_hip_logw_newton_loops import (AFFINE_SHAPES, L, PARAMS, SHAPES as LOOP_SHAPES, THETA, assert_newton_regime, bits, case,
@@ -158,6 +159,29 @@ def test_the_fp64_pass_keeps_its_bits_beside_this_one(bioen_amd):
         assert np.array_equal(ctx.logw_cov(g=g, G=G, theta=THETA)[0], Cf)
     with bioen_amd.Context(yT, YT) as ctx:
         assert np.array_equal(ctx.logw_cov_bf16(g=g, G=G, theta=THETA)[0], Cb)
+
+
+@pytest.mark.parametrize("shape", [(7, 37), (129, 257), (513, 1537)], ids=case_id)
+def test_cov_bf16_equals_forces_gram_bf16s_at_the_same_weights(bioen_amd, shape):
+    """g = G against forces = 0 with w0 = softmax(G): the same weights, the two instances of the one split-BF16 loop
+    (fgram.hpp: fgram16_pass) held to each other.  Each lies within (ii) of its restatement (the same loop, the same
+    derivation) and the two restatements (forces.hessian_gram_bf16_bioen_log_posterior_base, log_weights.
+    dual_newton_covariance_bf16) agree to the rounding of the weights, at most 1.2e-15 max|C| at these shapes on the host:
+    |C~_logw - C~_forces|_ik <= 2 . 48 tg 2^-23 s_ik + GATE max|C| + the FP64 floor"""
+    yT, YT, G, _ = logw_problem(shape)
+    w0 = np.exp(G - G.max())
+    w0 /= w0.sum()
+    S, floor = scale_matrix(yT, YT, G)
+    with bioen_amd.Context(yT, YT) as ctx:
+        fg_before = ctx.forces_gram_bf16(forces=np.zeros(shape[0]), w0=w0, theta=THETA)
+        Cb, _, _ = ctx.logw_cov_bf16(g=G, G=G, theta=THETA)
+        tg = gram_tg(ctx, shape[0])
+        D, top = np.abs(Cb - fg_before[0]), float(np.abs(fg_before[0]).max())
+        print("%dx%d: tg %d; |C~_logw - C~_forces| = %.3g s_ik (bound %.3g), %.3g max|C|"
+              % (shape + (tg, float((D[S > 0] / S[S > 0]).max()), 2 * 48 * tg * U23, float(D.max()) / top)))
+        assert (D <= 2 * 48 * tg * U23 * S + FORCES_GATE * top + floor).all()
+        fg_after = ctx.forces_gram_bf16(forces=np.zeros(shape[0]), w0=w0, theta=THETA)  # forces_gram_bf16's bits stay what they are
+        assert all(np.array_equal(a, b) for a, b in zip(fg_before, fg_after))
 
 
 # ---- the step, exactly ---------------------------------------------------------------------------------------------------

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """SHA-256 of the bytes of every output of the dense forces entries (forces_gram, forces_gram_bf16, forces_colquad,
 opt_newton_forces, forces_newton_factor / _solve, forces_inverse, forces_laplace) and of the log-weights
-dense entries (logw_cov, opt_dual_newton_logw, with logw_hessp at their point) on seeded synthetic contexts, as
-JSON: two builds of the library that print the same digests compute the same bits.
+dense entries (logw_cov, opt_dual_newton_logw, with logw_hessp at their point; logw_cov_bf16 and
+opt_dual_newton_logw_series over three theta from both covariance sources, its statuses and `switched` in clear)
+on seeded synthetic contexts, as JSON: two builds of the library that print the same digests compute the same bits.
 
     python3 tools/forces_dense_digest.py > new.json
     BIOEN_HIP_LIBRARY=/path/to/other/libbioen_hip.so python3 tools/forces_dense_digest.py > old.json
@@ -20,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np          # noqa: E402
 
 THETA = 10.0
+SERIES_THETAS = [1000.0, 10.0, 0.316]
 CASES = ["28x300", "65x257", "129x257", "205x1000", "513x1537", "1024x2049", "129x257:affine", "513x1537:affine",
          "129x257:segments1"]
 
@@ -99,6 +101,17 @@ def run_case(case):
             out["opt_dual_newton_logw"] = sha(*(dn[k] for k in sorted(dn)))
             out["logw_cov() at the optimum"] = sha(ctx.logw_cov())
             out["dual_newton_status"] = dn["status"]
+            # the split-BF16 covariance and the theta series, draws of their own again
+            srng = np.random.default_rng(M * N + 2)
+            g = G + 0.1 * srng.standard_normal(N)
+            out["logw_cov_bf16(g)"] = sha(*ctx.logw_cov_bf16(g=g, G=G, theta=THETA))
+            out["logw_cov_bf16()"] = sha(ctx.logw_cov_bf16())
+            for source, warm in (("gram_bf16", True), ("gram_bf16", False), ("gram", True)):
+                tag = "%s, %s" % (source, "warm" if warm else "cold")
+                ser = ctx.opt_dual_newton_logw_series(SERIES_THETAS, g, G, dict(gtol=1e-8), hessian=source, warm=warm)
+                out["opt_dual_newton_logw_series(%s)" % tag] = sha(*(r[k] for r in ser for k in sorted(r)))
+                out["series_status(%s)" % tag] = [r["status"] for r in ser]
+                out["series_switched(%s)" % tag] = [int(r["switched"]) for r in ser]
     finally:
         if segments is None:
             os.environ.pop("BIOEN_HIP_SEGMENTS", None)
