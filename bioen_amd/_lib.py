@@ -555,7 +555,11 @@ class Context(object):
         which = 2: the streaming pair on the row-major matrix (what serves a context without strip copies; answered whether
         or not the context is on it -- pair it with footprint() == {"rowmajor"} after the first evaluation): "sps": 128-column
         steps per segment, "gs": column tiles per segment, "tc": steps per tile, "nch": rows a wave of the adjoint kernel
-        walks, "fold": 1 = non-temporal matrix loads, "local_segments"."""
+        walks, "fold": 1 = non-temporal matrix loads, "local_segments".
+        which = 3: the forces method's dense Gram passes (forces_gram, forces_gram_bf16): "gs": sets per segment, "tc": the
+        longest chain of strips a set adds up, "nch": sets in all, "fold": tile pairs.  which = 4: forces_colquad's pass:
+        "sps": panels of 32 columns, "gs": blocks of the launch, "tc": the most panels a block runs, "nch": 64-row slices of
+        a strip (the kernel's NB), "fold": the strips' padded rows."""
         o = [C.c_int(0) for _ in range(6)]
         check(lib().bioen_hip_ctx_strip_plan(self._h, int(which), *[C.byref(v) for v in o]))
         return dict(zip(("sps", "gs", "tc", "nch", "fold", "local_segments"), (v.value for v in o)))

@@ -1011,8 +1011,30 @@ int bioen_hip_ctx_layout(const bioen_hip_ctx* c, int* one_copy, int* interleave,
 int bioen_hip_ctx_strip_plan(const bioen_hip_ctx* c, int pass, int* sps, int* gs, int* tc, int* nch, int* fold,
                              int* local_segments) {
     if (int rc = enter(c, FX_NONE, __func__)) return rc;
-    if (pass < 0 || pass > 2)
-        return fail(BIOEN_HIP_EINVAL, "bioen_hip_ctx_strip_plan: pass is 0 (log-weights forward), 1 (forces) or 2 (the streaming pair)");
+    if (pass < 0 || pass > 4)
+        return fail(BIOEN_HIP_EINVAL, "bioen_hip_ctx_strip_plan: pass is 0 (log-weights forward), 1 (forces), 2 (the streaming pair), "
+                                      "3 (the forces Gram passes) or 4 (the forces quadratic-form pass)");
+    if (pass == 3) {       // the forces method's dense Gram passes: what launch_forces_gram takes (kernels_forces_gram.hip)
+        const GramPlan p = forces_gram_plan(c);
+        const int s = strip_sets(c).sps;
+        if (sps) *sps = s;
+        if (gs) *gs = p.gs;
+        if (tc) *tc = (s + p.gs - 1) / p.gs;
+        if (nch) *nch = p.nsets;
+        if (fold) *fold = p.ntiles;
+        if (local_segments) *local_segments = c->vr;
+        return 0;
+    }
+    if (pass == 4) {       // the quadratic-form pass: launch_forces_colquad's grid (kernels_forces_colquad.hip)
+        const ColquadGrid g = forces_colquad_grid(c);
+        if (sps) *sps = g.npanels;
+        if (gs) *gs = g.blocks;
+        if (tc) *tc = (g.npanels + g.blocks - 1) / g.blocks;
+        if (nch) *nch = g.nb;
+        if (fold) *fold = g.mps;
+        if (local_segments) *local_segments = c->vr;
+        return 0;
+    }
     if (pass == 2) {       // the streaming pair on the row-major matrix: the context fields its launchers pass (kernels_matrix.hip)
         if (sps) *sps = c->segcols / 128;
         if (gs) *gs = c->fwd_ctiles / c->vr;

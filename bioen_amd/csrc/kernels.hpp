@@ -250,6 +250,11 @@ constexpr int kForcesColquadCols = 32;      // columns of a panel: one block own
 constexpr int kForcesColquadBlocks = 256;   // blocks of a launch (one per CU); block b runs the panels b, b + 256, ...
 // P: (strip rows)^2 doubles, zero beyond m, symmetric; ybar: the point's ybar'; out: n values
 void launch_forces_colquad(bioen_hip_ctx* c, const double* P, const double* ybar, double* out);
+struct ColquadGrid {                // the launch: block b of `blocks` runs the panels b, b + blocks, ... of `npanels`
+    int npanels, blocks;
+    int mps, nb;                    // the strips' padded rows; their 64-row slices (the kernel's NB)
+};
+ColquadGrid forces_colquad_grid(const bioen_hip_ctx* c);      // (bioen_hip_ctx_strip_plan reports it)
 
 // ---- forces N-vector kernels (blockIdx.y = batch position) ---------------------------------
 struct ForcesRound {

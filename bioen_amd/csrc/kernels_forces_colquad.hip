@@ -178,23 +178,31 @@ __global__ __launch_bounds__(256, 1) void k_forces_colquad(ColquadArgs q) {
 // ---- host side ------------------------------------------------------------------------------------
 // P: (strip rows)^2 doubles, zero beyond m; ybar: the kept point's ybar'; out: >= n doubles.  One block per CU (256), each
 // running the panels b, b + 256, ...
+ColquadGrid forces_colquad_grid(const bioen_hip_ctx* c) {
+    ColquadGrid g{};
+    g.npanels = (c->n + kForcesColquadCols - 1) / kForcesColquadCols;
+    g.blocks = std::min(g.npanels, kForcesColquadBlocks);
+    g.mps = panel_mps(c, 0);
+    g.nb = (g.mps + kWaveRows - 1) / kWaveRows;               // row blocks of T per wave: 1 .. 16
+    return g;
+}
+
 void launch_forces_colquad(bioen_hip_ctx* c, const double* P, const double* ybar, double* out) {
+    const ColquadGrid g = forces_colquad_grid(c);
     ColquadArgs q{};
     q.Ys = c->Ys[0];
     q.center = c->strip_center;
     q.ybar = ybar;
     q.P = P;
     q.out = out;
-    q.mps = panel_mps(c, 0);
+    q.mps = g.mps;
     q.m = c->m;
     q.n = c->n;
     q.sps = strip_sps(c);
     q.ilv = strip_ilv(c);
-    q.npanels = (c->n + kForcesColquadCols - 1) / kForcesColquadCols;
-    const int nblk = std::min(q.npanels, kForcesColquadBlocks);
-    const int nb = (q.mps + kWaveRows - 1) / kWaveRows;         // row blocks of T per wave: 1 .. 16
-    for_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(nb, [&](auto NB) {
-        hipLaunchKernelGGL(k_forces_colquad<NB.value>, dim3(nblk), dim3(256), 0, c->stream, q);
+    q.npanels = g.npanels;
+    for_value<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(g.nb, [&](auto NB) {
+        hipLaunchKernelGGL(k_forces_colquad<NB.value>, dim3(g.blocks), dim3(256), 0, c->stream, q);
     });
 }
 

@@ -192,6 +192,11 @@ int bioen_hip_ctx_layout(const bioen_hip_ctx* ctx, int* one_copy, int* interleav
  * whether or not the context is on it at the moment -- sps: 128-column steps per segment, gs: column tiles per segment, tc:
  * steps per tile (a segment's last tile is cut at the segment's end), nch: rows a wave of the adjoint kernel walks, fold:
  * 1 = the passes use non-temporal loads, local_segments as above.
+ * pass 3: the forces method's dense Gram passes (bioen_hip_forces_gram, _gram_bf16; M <= 1024) -- sps as above, gs: sets
+ * per segment (set g chains the strips g, g + gs, ...), tc: the longest chain, ceil(sps / gs), nch: sets in all, fold: tile
+ * pairs of 128 rows.  pass 4: the quadratic-form pass (bioen_hip_forces_colquad) -- sps: panels of 32 columns, gs: blocks
+ * of the launch (block b runs the panels b, b + gs, ...), tc: the most panels a block runs, nch: the 64-row slices of a
+ * strip (the kernel's NB), fold: the strips' padded rows.
  * Any result pointer may be NULL; another pass is BIOEN_HIP_EINVAL.  For tests that must prove a slot ran several strips
  * of a segment, or a tile several steps. */
 int bioen_hip_ctx_strip_plan(const bioen_hip_ctx* ctx, int pass, int* sps, int* gs, int* tc, int* nch, int* fold,
