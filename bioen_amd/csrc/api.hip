@@ -45,11 +45,8 @@ int fail(int code, const char* msg) {
 
 const std::string& last_error() { return g_last_error; }
 
-static void bfgs_free(bioen_hip_ctx* c);      // dense inverse-Hessian BFGS session (api_bfgs.inl)
-static void hessp_free(bioen_hip_ctx* c);     // the buffers of the Hessian-vector products (api_hessp.inl)
-
-// The point a Hessian-vector product refers to (api_hessp.inl) is gone; `by`: an entry's name, or what failed
-static void point_drop(bioen_hip_ctx* c, const char* by) {
+// The point a Hessian-vector product refers to (api_hessp.cpp) is gone; `by`: an entry's name, or what failed
+void point_drop(bioen_hip_ctx* c, const char* by) {
     c->fgram_fresh = 0;
     if (c->point_valid) {
         c->point_valid = 0;
@@ -76,7 +73,7 @@ int enter(const bioen_hip_ctx* ctx, unsigned fx, const char* who) {
 // ---------------------------------------------------------------------------------
 // allocation helpers
 // ---------------------------------------------------------------------------------
-static int dalloc_zero(double** p, size_t count, hipStream_t s) {
+int dalloc_zero(double** p, size_t count, hipStream_t s) {
     *p = nullptr;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(double));
     if (e != hipSuccess) {
@@ -85,6 +82,17 @@ static int dalloc_zero(double** p, size_t count, hipStream_t s) {
     }
     BIOEN_HIP_CHECK(hipMemsetAsync(*p, 0, count * sizeof(double), s));
     return 0;
+}
+
+// The forces method's pinned staging buffer (ctx.hpp: host_m), on first need: ForcesBatchEngine's constructor and the forces
+// Hessian-vector products (api_forces_hessp.cpp: fhp_products) pack their M-vectors there.  The products need nothing else
+// of an engine: its other lazy allocation, the live_f page, is read by the engine's own rounds only, and is there anyway --
+// a forces point exists only after fhp_set_point -> forces_eval has constructed an engine on the context.
+int forces_staging(bioen_hip_ctx* c) {
+    if (c->host_m) return 0;
+    const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&c->host_m), 2 * (size_t)c->mp * kMaxBatch * sizeof(double),
+                                       hipHostMallocDefault);
+    return e == hipSuccess ? 0 : hip_fail(e, "hipHostMalloc", __FILE__, __LINE__);
 }
 
 // (per SEGMENT: the tiles are those of a GPU holding one segment; a context with vr of them has vr x as many)
@@ -315,7 +323,7 @@ static bool staged_upload_forced() {
     return e && e[0] == '1';
 }
 
-static int h2d_user(bioen_hip_ctx* c, void* dst, const void* src, size_t bytes) {
+int h2d_user(bioen_hip_ctx* c, void* dst, const void* src, size_t bytes) {
     const hipError_t e = staged_upload_forced() ? hipErrorInvalidValue
                                                 : hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipErrorInvalidValue) {
@@ -340,7 +348,7 @@ static int h2d_user_2d(bioen_hip_ctx* c, void* dst, size_t dpitch, const void* s
 
 // The same towards a caller's buffer: device -> host.  The staged form is synchronous on `stream` and brings its own pinned
 // chunk (the result deliveries run on threads of their own: nothing shared).
-static hipError_t d2h_user(hipStream_t stream, void* dst, const void* src, size_t bytes) {
+hipError_t d2h_user(hipStream_t stream, void* dst, const void* src, size_t bytes) {
     hipError_t e = staged_upload_forced() ? hipErrorInvalidValue : hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream);
     if (e != hipErrorInvalidValue) return e;
     (void)hipGetLastError();
@@ -357,7 +365,7 @@ static hipError_t d2h_user(hipStream_t stream, void* dst, const void* src, size_
     return e;
 }
 
-static hipError_t d2h_user_2d(hipStream_t stream, char* dst, size_t dpitch, const char* src, size_t spitch, size_t width, size_t height) {
+hipError_t d2h_user_2d(hipStream_t stream, char* dst, size_t dpitch, const char* src, size_t spitch, size_t width, size_t height) {
     hipError_t e = staged_upload_forced() ? hipErrorInvalidValue
                                           : hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToHost, stream);
     if (e != hipErrorInvalidValue) return e;
@@ -370,12 +378,12 @@ static hipError_t d2h_user_2d(hipStream_t stream, char* dst, size_t dpitch, cons
 }
 
 // host N-vectors are always GLOBAL (n_global long); a sharded context takes its slice
-static int upload_n(bioen_hip_ctx* c, double* dst, const double* src) {
+int upload_n(bioen_hip_ctx* c, double* dst, const double* src) {
     return h2d_user(c, dst, src + c->col0, (size_t)c->n * sizeof(double));
 }
 
 // gather a sharded device N-vector into a GLOBAL host vector (world == 1: plain download)
-static int download_n(bioen_hip_ctx* c, double* dst_global, const double* src_local) {
+int download_n(bioen_hip_ctx* c, double* dst_global, const double* src_local) {
     if (c->world == 1) {
         BIOEN_HIP_CHECK(d2h_user(c->stream, dst_global, src_local, (size_t)c->n * sizeof(double)));
         return 0;
@@ -394,7 +402,7 @@ static int download_n(bioen_hip_ctx* c, double* dst_global, const double* src_lo
     return 0;
 }
 
-static int read_scalars(bioen_hip_ctx* c, int nslots = 1) {
+int read_scalars(bioen_hip_ctx* c, int nslots) {
     BIOEN_HIP_CHECK(hipMemcpyAsync(c->host_scal, c->scal, (size_t)nslots * kScalStride * sizeof(double),
                                    hipMemcpyDeviceToHost, c->stream));
     BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -437,7 +445,7 @@ static int enqueue_logs0(bioen_hip_ctx* c, const Round& r) {
     return 0;
 }
 
-static int check_launch() {
+int check_launch() {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "kernel launch", __FILE__, __LINE__);
     return 0;
@@ -449,7 +457,7 @@ static void print_summary(const bioen_hip_ctx* c, const bioen_opt_result& r);
 // ---------------------------------------------------------------------------------
 // evaluation pipelines (all asynchronous on c->stream)
 // ---------------------------------------------------------------------------------
-static Round make_round(bioen_hip_ctx* c, const int* slots, int k, const double* stp, const double* theta) {
+Round make_round(bioen_hip_ctx* c, const int* slots, int k, const double* stp, const double* theta) {
     Round r{};
     r.n = k;
     for (int a = 0; a < k; ++a) {
@@ -471,14 +479,13 @@ static Round make_round(bioen_hip_ctx* c, const int* slots, int k, const double*
 
 // log-weights: r.x must hold the points and P_MAX their block maxima (launch_trial does both).
 // (the caller has produced this rank's block maxima in its X_MAX segment; they are not exchanged)
-static int enqueue_logw_adjoint(bioen_hip_ctx* c, const Round& r);
 
 // The pass family of a product with the matrix on the log-weights side, decided and made ready: *nblk > 0, the strip kernels
 // (the blocks of fwd_strip_blocks; the row-sum order copy is there in `method`'s layout, with `colsum` the column-sum order
 // one too: every copy before the first pass, so that one evaluation never mixes the two families), or *nblk = 0, the
 // streaming kernels on the row-major matrix, which is there.  A copy that cannot be allocated switches the context to the
 // streaming kernels for good (strips_unavailable).  strips_ok = false: the caller has reasons of its own against the strips.
-static int choose_logw_passes(bioen_hip_ctx* c, bool strips_ok, int method, bool colsum, int* nblk) {
+int choose_logw_passes(bioen_hip_ctx* c, bool strips_ok, int method, bool colsum, int* nblk) {
     *nblk = strips_ok ? fwd_strip_blocks(c) : 0;
     if (*nblk > 0) {
         int rc = ensure_strip_copy(c, method);
@@ -489,7 +496,7 @@ static int choose_logw_passes(bioen_hip_ctx* c, bool strips_ok, int method, bool
     return *nblk > 0 ? 0 : ensure_rowmajor(c);
 }
 
-static int enqueue_logw_eval(bioen_hip_ctx* c, const Round& r, bool with_grad) {
+int enqueue_logw_eval(bioen_hip_ctx* c, const Round& r, bool with_grad) {
     int rc, nblk;
     c->last_width = r.n;
     c->last_pos = 0;
@@ -517,7 +524,7 @@ static int enqueue_logw_eval(bioen_hip_ctx* c, const Round& r, bool with_grad) {
 
 // second half of an evaluation; needs w, scal[S_P] and the compact ybar_c / r_c of the SAME round
 // still in place (nothing else evaluated in between)
-static int enqueue_logw_adjoint(bioen_hip_ctx* c, const Round& r) {
+int enqueue_logw_adjoint(bioen_hip_ctx* c, const Round& r) {
     int rc;
     MVec8 out{};
     for (int a = 0; a < r.n; ++a) out.p[a] = r.a[a];
@@ -538,9 +545,9 @@ static int enqueue_logw_adjoint(bioen_hip_ctx* c, const Round& r) {
 }
 
 // One evaluation of the round's single point, start to finish: log sum exp of the prior, the point's maxima, f and (with_grad)
-// the gradient in r.g[0]; keep_point: and what the Hessian-vector products keep of it (api_hessp.inl).  -> *f; grad_out (a
+// the gradient in r.g[0]; keep_point: and what the Hessian-vector products keep of it (api_hessp.cpp).  -> *f; grad_out (a
 // caller's global N-vector) if given; the round's scalars in host_scal
-static int eval_logw_point(bioen_hip_ctx* c, const Round& r, bool with_grad, bool keep_point, double* f, double* grad_out) {
+int eval_logw_point(bioen_hip_ctx* c, const Round& r, bool with_grad, bool keep_point, double* f, double* grad_out) {
     int rc;
     if ((rc = enqueue_logs0(c, r))) return rc;
     launch_max(c, r);
@@ -743,6 +750,52 @@ static void resolve_timers(bioen_hip_ctx* c) {
         t.pool.push_back(p);
     }
     t.pending.clear();
+}
+
+// ---- the forces method's guard and evaluation (host.hpp) --------------------------------------------------
+static bool is_affine(const bioen_hip_ctx* c) { return c->affine; }
+
+// the forces evaluation in canonical segments: the two-pass strip kernels (M <= 1024) or the row panels (M > 1024)
+static bool forces_canonical(const bioen_hip_ctx* c) {
+    return forces_fused_blocks(c) > 0 || (strip_panels(c) && fwd_strip_blocks(c) > 0);
+}
+
+int forces_guard(const bioen_hip_ctx* c, bool strip_path_ok) {
+    // sharded contexts run the forces method in canonical segments only (not on the r01 streaming kernels)
+    if (c->world != 1 && !(strip_path_ok && forces_canonical(c)))
+        return fail(BIOEN_HIP_ESTATE, strip_path_ok ? kForcesNeedsStrips : "not available on this structure-sharded context");
+    if (is_affine(c) && c->storage)          // the experiment's copies are pre-centred and its passes carry no offset
+        return fail(BIOEN_HIP_ESTATE, "the affine observable model is not served on the reduced-storage experiment's copies "
+                                      "(bioen_hip_ctx_set_storage(0), or remove the model)");
+    if (c->storage && !(strip_path_ok && forces_fused_blocks(c) > 0))
+        return fail(BIOEN_HIP_ESTATE, "the reduced-storage experiment serves the strip passes (M <= 1024) only");
+    return 0;
+}
+
+// k evaluations that share every matrix pass (slots 0 .. k-1); forces [k][m], grad [k][m]
+int forces_eval(bioen_hip_ctx* c, int k, const double* forces, const double* w0, const double* thetas, double* f, double* grad) {
+    int rc = forces_guard(c);
+    if (rc) return rc;
+    for (int s = 0; s < k; ++s)
+        if ((rc = alloc_slot(c, s, false))) return rc;
+    if ((rc = upload_n(c, c->fixed, w0))) return rc;
+    bioen_lbfgs_config dummy{};
+    ForcesBatchEngine eng(c, dummy, false);
+    int slots[kMaxBatch];
+    const double* pt[kMaxBatch];
+    for (int a = 0; a < k; ++a) {
+        slots[a] = a;
+        pt[a] = forces + (size_t)a * c->m;
+    }
+    eng.evaluate(slots, k, pt, thetas, grad != nullptr);
+    if (eng.rc) return eng.rc;
+    for (int a = 0; a < k; ++a) {
+        if (grad)
+            for (int i = 0; i < c->m; ++i) grad[(size_t)a * c->m + i] = eng.gm_h[(size_t)i * k + a];
+        if (f) f[a] = c->host_scal[(size_t)a * kScalStride + S_F];
+    }
+    if (k > 1) c->last_width = 0;
+    return 0;
 }
 
 }  // namespace bioen
@@ -1073,7 +1126,7 @@ int bioen_hip_ctx_footprint(const bioen_hip_ctx* c, int* forms, long long* bytes
         if (c->Yr) { f |= 8; b += each; }
         if (c->Yr1) { f |= 8; b += each; }
     }
-    if (c->bfgs) {               // the live BFGS session's inverse Hessian (api_bfgs.inl)
+    if (c->bfgs) {               // the live BFGS session's inverse Hessian (api_bfgs.cpp)
         f |= 16;
         b += c->bfgs_hbytes;
     }
@@ -1264,52 +1317,6 @@ int bioen_hip_opt_lbfgs_logw(bioen_hip_ctx* c, const double* g0, const double* G
 }
 
 // ---- forces ---------------------------------------------------------------------------
-static bool is_affine(const bioen_hip_ctx* c) { return c->affine; }
-
-// the forces evaluation in canonical segments: the two-pass strip kernels (M <= 1024) or the row panels (M > 1024)
-static bool forces_canonical(const bioen_hip_ctx* c) {
-    return forces_fused_blocks(c) > 0 || (strip_panels(c) && fwd_strip_blocks(c) > 0);
-}
-
-static int forces_guard(const bioen_hip_ctx* c, bool strip_path_ok = true) {
-    // sharded contexts run the forces method in canonical segments only (not on the r01 streaming kernels)
-    if (c->world != 1 && !(strip_path_ok && forces_canonical(c)))
-        return fail(BIOEN_HIP_ESTATE, strip_path_ok ? kForcesNeedsStrips : "not available on this structure-sharded context");
-    if (is_affine(c) && c->storage)          // the experiment's copies are pre-centred and its passes carry no offset
-        return fail(BIOEN_HIP_ESTATE, "the affine observable model is not served on the reduced-storage experiment's copies "
-                                      "(bioen_hip_ctx_set_storage(0), or remove the model)");
-    if (c->storage && !(strip_path_ok && forces_fused_blocks(c) > 0))
-        return fail(BIOEN_HIP_ESTATE, "the reduced-storage experiment serves the strip passes (M <= 1024) only");
-    return 0;
-}
-
-// k evaluations that share every matrix pass (slots 0 .. k-1); forces [k][m], grad [k][m]
-static int forces_eval(bioen_hip_ctx* c, int k, const double* forces, const double* w0, const double* thetas, double* f,
-                       double* grad) {
-    int rc = forces_guard(c);
-    if (rc) return rc;
-    for (int s = 0; s < k; ++s)
-        if ((rc = alloc_slot(c, s, false))) return rc;
-    if ((rc = upload_n(c, c->fixed, w0))) return rc;
-    bioen_lbfgs_config dummy{};
-    ForcesBatchEngine eng(c, dummy, false);
-    int slots[kMaxBatch];
-    const double* pt[kMaxBatch];
-    for (int a = 0; a < k; ++a) {
-        slots[a] = a;
-        pt[a] = forces + (size_t)a * c->m;
-    }
-    eng.evaluate(slots, k, pt, thetas, grad != nullptr);
-    if (eng.rc) return eng.rc;
-    for (int a = 0; a < k; ++a) {
-        if (grad)
-            for (int i = 0; i < c->m; ++i) grad[(size_t)a * c->m + i] = eng.gm_h[(size_t)i * k + a];
-        if (f) f[a] = c->host_scal[(size_t)a * kScalStride + S_F];
-    }
-    if (k > 1) c->last_width = 0;
-    return 0;
-}
-
 int bioen_hip_forces_weights(bioen_hip_ctx* c, const double* forces, const double* w0, double* w) {
     if (int rc = enter(c, FX_EVALUATES, __func__)) return rc;
     if (!forces || !w0 || !w) return fail(BIOEN_HIP_EINVAL, "NULL argument");
@@ -1603,12 +1610,3 @@ int bioen_hip_read_probe(bioen_hip_ctx* c, int form, int reps, double* gbytes_pe
 }  // extern "C"
 
 #include "api_multimin.inl"
-#include "api_bfgs.inl"
-#include "api_forces_point.inl"
-#include "api_hessp.inl"
-#include "api_forces_hessp.inl"
-#include "api_forces_gram.inl"
-#include "api_forces_colquad.inl"
-#include "api_forces_newton.inl"
-#include "api_forces_laplace.inl"
-#include "api_logw_newton.inl"

@@ -1,4 +1,5 @@
-// Dense inverse-Hessian BFGS session on a log-weights context (part of api.hip's translation unit).
+// Dense inverse-Hessian BFGS session on a log-weights context (what it calls of the core: host.hpp; BfgsSession is an
+// incomplete type everywhere else).
 //
 // The host driver (bioen_amd/bfgs.py) runs scipy's fmin_bfgs loop on scipy's own scalar line searches; this session
 // is its vector backend: the point, the gradient, the direction, the step pairs and the N x N inverse Hessian H stay in
@@ -12,6 +13,14 @@
 //
 // A session lives on an UNSHARDED context only.  Which other calls on the context end it is each entry's declaration to
 // the guard (host.hpp: enter); every error inside a bfgs call ends it too, and bioen_hip_ctx_destroy.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <utility>
+
+#include "host.hpp"
+#include "kernels.hpp"
 
 namespace bioen {
 
@@ -35,7 +44,7 @@ struct BfgsSession {
     long long passes = 0;              // H passes run
 };
 
-static void bfgs_free(bioen_hip_ctx* c) {
+void bfgs_free(bioen_hip_ctx* c) {
     if (!c || !c->bfgs) return;
     BfgsSession* S = c->bfgs;
     if (c->stream) hipStreamSynchronize(c->stream);
@@ -224,6 +233,8 @@ static int bfgs_update(bioen_hip_ctx* c, BfgsSession* S, double* dphi0, int* rho
 }
 
 }  // namespace bioen
+
+using namespace bioen;
 
 extern "C" {
 

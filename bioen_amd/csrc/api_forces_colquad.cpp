@@ -1,6 +1,11 @@
-// One quadratic form per structure at a kept forces point (part of api.hip's translation unit: uses its static helpers;
-// kernel: kernels_forces_colquad.hip; the mathematics: DESIGN section 6f).  The point, the guard and the buffer are
-// api_forces_point.inl's: forces_point_prologue, dense_guard with this entry's reasons, ensure_scratch.
+// One quadratic form per structure at a kept forces point (kernel: kernels_forces_colquad.hip; the mathematics: DESIGN
+// section 6f).  The point, the guard and the buffer are api_forces_point.cpp's: forces_point_prologue, dense_guard with
+// this entry's reasons, ensure_scratch.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "dense.hpp"
 
 namespace bioen {
 
@@ -17,6 +22,8 @@ static bool fcolquad_symmetric(const double* P, int m) {
 }
 
 }  // namespace bioen
+
+using namespace bioen;
 
 extern "C" int bioen_hip_forces_colquad(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, const double* P,
                                         double* out, double* f, double* grad) {

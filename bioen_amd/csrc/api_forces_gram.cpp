@@ -1,16 +1,16 @@
-// The dense Hessian and the covariance of the forces objective in one pass (part of api.hip's translation unit: uses its
-// static helpers), from FP64 operands -- bioen_hip_forces_gram; kernels: kernels_forces_gram.hip; DESIGN section 6e -- or
+// The dense Hessian and the covariance of the forces objective in one pass, from FP64 operands -- bioen_hip_forces_gram; kernels: kernels_forces_gram.hip; DESIGN section 6e -- or
 // from split-BF16 operands on the BF16 matrix cores, for a Newton minimizer -- bioen_hip_forces_gram_bf16; kernel:
 // k_forces_gram_bf16, in the same file; DESIGN section 6g.  Two entries, not two modes of one: each pass has a buffer of its own,
 // so that bioen_hip_forces_gram's results stay bitwise what they are.  Everything else is one function, fgram_entry; the
-// point, the guard and the buffers are api_forces_point.inl's.
+// point, the guard and the buffers are api_forces_point.cpp's.
+#include "dense.hpp"
 
 namespace bioen {
 
 // C and H of the kept forces point into the buffer of `source` (0: the FP64 pass, SCRATCH_GRAM; 1: the split-BF16 pass,
 // SCRATCH_GRAM16), not downloaded: *cov, *hess (either may be NULL) <- where they stand on the device.  The Newton
-// entries (api_forces_newton.inl) take their Hessian from here.
-static int fgram_compute(bioen_hip_ctx* c, int source, const double** cov, const double** hess) {
+// entries (api_forces_newton.cpp) take their Hessian from here.
+int fgram_compute(bioen_hip_ctx* c, int source, const double** cov, const double** hess) {
     int rc;
     if (!source) c->fgram_fresh = 0;
     if (forces_fused_blocks(c) <= 0) return fail(BIOEN_HIP_ESTATE, "the strip passes no longer serve this context");
@@ -47,6 +47,8 @@ static int fgram_entry(bioen_hip_ctx* c, int source, const double* forces, const
 }
 
 }  // namespace bioen
+
+using namespace bioen;
 
 extern "C" int bioen_hip_forces_gram(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* cov,
                                      double* hess, double* f, double* grad) {

@@ -1,12 +1,16 @@
-// Hessian-vector products of the forces objective (part of api.hip's translation unit: uses its static helpers; kernels:
-// kernels_forces_hessp.hip and the SM_TANGENT / SM_PRODUCT forms of k_strip / k_strip2; the mathematics: DESIGN section 6d).
+// Hessian-vector products of the forces objective (kernels: kernels_forces_hessp.hip and the SM_TANGENT / SM_PRODUCT forms
+// of k_strip / k_strip2; the mathematics: DESIGN section 6d).
 //
 // A call with forces != NULL is bioen_hip_forces_fdf with a gradient, launch for launch, after which the context keeps
 // "the point" (ctx.hpp: point_kind 1): slot 0 holds x' and the scalars, c->fixed the prior w0, fpoint_ybar / fpoint_rs the
 // M-vectors ybar' and r o s, fpoint_q the N-vector q - qbar -- ONE column-sum pass more than the evaluation.  A product at
 // the kept point is then two fused matrix passes, what a gradient costs, for up to kMaxBatch directions at once.
-// Whether a call sets the point or serves the kept one, and the refusal without one, is api_forces_point.inl's
+// Whether a call sets the point or serves the kept one, and the refusal without one, is api_forces_point.cpp's
 // forces_point_prologue, shared with the dense entries.
+#include <algorithm>
+#include <vector>
+
+#include "dense.hpp"
 
 namespace bioen {
 
@@ -24,7 +28,7 @@ static int fhp_buffers(bioen_hip_ctx* c, int k) {
 }
 
 // what the entry refuses beyond forces_guard: everything but the fused strip passes on the FP64 copy
-static int fhp_guard(const bioen_hip_ctx* c) {
+int fhp_guard(const bioen_hip_ctx* c) {
     if (c->storage)
         return fail(BIOEN_HIP_ESTATE, "bioen_hip_forces_hessp is not served on the reduced-storage experiment's copies "
                                       "(bioen_hip_ctx_set_storage(0))");
@@ -51,9 +55,7 @@ static int fhp_download(bioen_hip_ctx* c, int k, double* hv, double* gm_h) {
 static int fhp_products(bioen_hip_ctx* c, int k, const double* v, double* hv) {
     int rc;
     if ((rc = fhp_buffers(c, k))) return rc;
-    bioen_lbfgs_config dummy{};
-    ForcesBatchEngine eng(c, dummy, false);             // (the pinned staging buffers)
-    if (eng.rc) return eng.rc;
+    if ((rc = forces_staging(c))) return rc;            // (c->host_m; the live page is the engine's own business: api.hip)
     const int m = c->m;
     const size_t cnt = (size_t)c->mp * k;
     double* um_h = c->host_m;
@@ -140,10 +142,10 @@ static int fhp_products(bioen_hip_ctx* c, int k, const double* v, double* hv) {
 }
 
 // Evaluates the point and keeps it on the context, for the entry `who` (every entry that goes through
-// api_forces_point.inl's forces_point_prologue, and the Newton loop): the effects are declared under that name, so the
+// api_forces_point.cpp's forces_point_prologue, and the Newton loop): the effects are declared under that name, so the
 // reason recorded for a dropped point names the call the user made.
-static int fhp_set_point(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* f, double* grad,
-                         const char* who) {
+int fhp_set_point(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* f, double* grad,
+                  const char* who) {
     int rc;
     if ((rc = enter(c, FX_EVALUATES, who))) return rc;
     c->point_lost = "a call that failed to set a new point";
@@ -183,6 +185,8 @@ static int fhp_set_point(bioen_hip_ctx* c, const double* forces, const double* w
 }
 
 }  // namespace bioen
+
+using namespace bioen;
 
 extern "C" int bioen_hip_forces_hessp(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, int k,
                                       const double* v, double* hv, double* f, double* grad) {

@@ -1,8 +1,13 @@
-// The Laplace error bars of the forces method without leaving the device (part of api.hip's translation unit: uses its
-// static helpers; kernels: kernels_forces_laplace.hip).  H stays where bioen_hip_forces_gram leaves it
-// (fgram_compute, the FP64 pass), is factorised by the Newton entries' kernels (fnewton_factor, lambda = 0) and inverted
-// from the factor; H^-1 is handed to k_forces_colquad where it stands.  Only what the caller asks for comes down.  The
-// guard, the refusal without a forces point and the buffers are api_forces_point.inl's, with these entries' wording.
+// The Laplace error bars of the forces method without leaving the device (kernels: kernels_forces_laplace.hip; DESIGN
+// section 6i).  H stays where bioen_hip_forces_gram leaves it (fgram_compute, the FP64 pass), is factorised by the Newton
+// entries' kernels (fnewton_factor, lambda = 0) and inverted from the factor; H^-1 is handed to k_forces_colquad where it
+// stands.  Only what the caller asks for comes down.  The guard, the refusal without a forces point and the buffers are
+// api_forces_point.cpp's, with these entries' wording.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "dense.hpp"
 
 namespace bioen {
 
@@ -73,6 +78,8 @@ static void flaplace_logdet(const std::vector<double>& ldiag, double* logdet, do
 }
 
 }  // namespace bioen
+
+using namespace bioen;
 
 extern "C" int bioen_laplace_forces_inverse(bioen_hip_ctx* c, const double* A, double* Ainv, double* logdet, int* info) {
     if (int rc = enter(c, FX_NONE, __func__)) return rc;      // a call rejected below leaves point, session and device alone

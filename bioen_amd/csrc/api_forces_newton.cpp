@@ -1,8 +1,14 @@
-// The forces method's own Newton minimizer (part of api.hip's translation unit: uses its static helpers; kernels:
-// kernels_forces_newton.hip).  The Hessian stays where bioen_hip_forces_gram / _gram_bf16 leave it
-// (api_forces_gram.inl: fgram_compute), is factorised and solved on the device; the M-vectors stay on the host, as in
-// ForcesBatchEngine; the loop is forces.py's newton_bioen_log_posterior_base, decision for decision.  The guard, the
-// refusal without a forces point and the buffer are api_forces_point.inl's, with these entries' wording.
+// The forces method's own Newton minimizer (kernels: kernels_forces_newton.hip).  The Hessian stays
+// where bioen_hip_forces_gram / _gram_bf16 leave it (api_forces_gram.cpp: fgram_compute), is factorised and solved on the
+// device; the M-vectors stay on the host, as in ForcesBatchEngine; the loop is forces.py's
+// newton_bioen_log_posterior_base, decision for decision.  The guard, the refusal without a forces point and the buffer
+// are api_forces_point.cpp's, with these entries' wording.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "dense.hpp"
 
 namespace bioen {
 
@@ -10,13 +16,7 @@ namespace bioen {
 static const PointWords kFNewtonPoint = {"call with forces",
                                          "set a forces point first (bioen_hip_forces_hessp, bioen_hip_forces_gram with forces)"};
 
-struct FNewtonBuf {
-    double *L, *A, *X, *dg;
-    int* info;
-    int ldl;
-};
-
-static FNewtonBuf fnewton_layout(const bioen_hip_ctx* c) {
+FNewtonBuf fnewton_layout(const bioen_hip_ctx* c) {
     FNewtonBuf b{};
     const size_t mp = (size_t)c->mp, m = (size_t)c->m;
     b.ldl = c->mp;
@@ -28,13 +28,13 @@ static FNewtonBuf fnewton_layout(const bioen_hip_ctx* c) {
     return b;
 }
 
-static int fnewton_buffers(bioen_hip_ctx* c) {
+int fnewton_buffers(bioen_hip_ctx* c) {
     const size_t mp = (size_t)c->mp, m = (size_t)c->m;
     return ensure_scratch(c, SCRATCH_NEWTON, mp * mp + m * m + (size_t)kMaxBatch * mp + mp + 2);
 }
 
 // chol(lower(src) + lambda I) -> the context's L; *info as LAPACK's; dmax (may be NULL): max |diag src|
-static int fnewton_factor(bioen_hip_ctx* c, const double* src, double lambda, int* info, double* dmax) {
+int fnewton_factor(bioen_hip_ctx* c, const double* src, double lambda, int* info, double* dmax) {
     int rc;
     const FNewtonBuf b = fnewton_layout(c);
     c->fnewton_state = 0;
@@ -72,6 +72,8 @@ static int fnewton_solve(bioen_hip_ctx* c, int k, const double* B, double* X) {
 }
 
 }  // namespace bioen
+
+using namespace bioen;
 
 extern "C" int bioen_hip_forces_newton_factor(bioen_hip_ctx* c, const double* A, int source, double lambda, double* L, int* info) {
     if (int rc = enter(c, FX_NONE, __func__)) return rc;      // a call rejected below leaves point, session and device alone

@@ -1,24 +1,16 @@
-// What the entries that work at a kept point share (part of api.hip's translation unit: uses its static helpers; included in
-// front of api_hessp.inl, the api_forces_*.inl files and api_logw_newton.inl): the refusal without a point of the right
-// kind, the prologues of the entries that set a point or serve the kept one -- the forces entries' and the log-weights
-// entries' --, the guard of the dense entries (M <= 1024, one GPU, the FP64 strip copies) and the scratch buffers the
-// context keeps for them.  DESIGN section 6c has the rules.
+// What the entries that work at a kept point share (declared in dense.hpp, for api_hessp.cpp, the api_forces_*.cpp files
+// and api_logw_newton.cpp): the refusal without a point of the right kind, the prologues of the entries that set a point or
+// serve the kept one -- the forces entries' and the log-weights entries' --, the guard of the dense entries (M <= 1024, one
+// GPU, the FP64 strip copies) and the scratch buffers the context keeps for them.  DESIGN section 6c has the rules.
+#include <string>
+
+#include "dense.hpp"
 
 namespace bioen {
 
-static int fhp_set_point(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* f, double* grad,
-                         const char* who);      // api_forces_hessp.inl
-static int hessp_buffers(bioen_hip_ctx* c, int k);      // api_hessp.inl
-
-// Where an entry's refusal without a point reads differently from the kind's own, it stands behind "<who>: " with these
-// words: last, the call whose point is gone; remedy, what to do about it
-struct PointWords {
-    const char *last, *remedy;
-};
-
 // 0 if the context keeps a point of `kind` (0: log-weights, 1: forces), else BIOEN_HIP_ESTATE and why there is none: it is
 // the other method's, it was dropped (by what), or none was ever set
-static int need_point(const bioen_hip_ctx* c, int kind, const char* who, const PointWords* words = nullptr) {
+int need_point(const bioen_hip_ctx* c, int kind, const char* who, const PointWords* words) {
     if (c->point_valid && c->point_kind == kind) return 0;
     static const struct { const char *name, *setter, *arg, *last; } kKind[2] = {
         {"log-weights", "bioen_hip_logw_hessp", "g", "bioen_hip_logw_hessp call with g"},
@@ -37,8 +29,8 @@ static int need_point(const bioen_hip_ctx* c, int kind, const char* who, const P
 
 // The point of a forces entry `who`: with forces it is an evaluation -- bioen_hip_forces_hessp's with k = 0, declared under
 // the entry's name -- that leaves a new point; without, the kept forces point serves, and the call only works on the device
-static int forces_point_prologue(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* f,
-                                 double* grad, const char* who) {
+int forces_point_prologue(bioen_hip_ctx* c, const double* forces, const double* w0, double theta, double* f, double* grad,
+                          const char* who) {
     if (forces) return fhp_set_point(c, forces, w0, theta, f, grad, who);
     if (int rc = need_point(c, 1, who)) return rc;
     return enter(c, FX_DEVICE, who);
@@ -46,7 +38,7 @@ static int forces_point_prologue(bioen_hip_ctx* c, const double* forces, const d
 
 // Slot 0's x (and c->fixed = G) hold a log-weights point: bioen_hip_logw_fdf's evaluation of it, launch for launch, after
 // which it is the context's kept point.  k: the directions hessp_buffers provides for
-static int logw_keep_point(bioen_hip_ctx* c, double theta, int k, double* f, double* grad) {
+int logw_keep_point(bioen_hip_ctx* c, double theta, int k, double* f, double* grad) {
     int rc;
     c->point_lost = "a call that failed to set a new point";
     if ((rc = hessp_buffers(c, k))) return rc;
@@ -61,8 +53,8 @@ static int logw_keep_point(bioen_hip_ctx* c, double theta, int k, double* f, dou
 
 // The point of a log-weights entry `who`, as forces_point_prologue: with g it is an evaluation at (g, G), declared under the
 // entry's name, that leaves a new point; without, the kept log-weights point serves
-static int logw_point_prologue(bioen_hip_ctx* c, const double* g, const double* G, double theta, int k, double* f,
-                               double* grad, const char* who, const PointWords* words = nullptr) {
+int logw_point_prologue(bioen_hip_ctx* c, const double* g, const double* G, double theta, int k, double* f, double* grad,
+                        const char* who, const PointWords* words) {
     int rc;
     if (!g) return (rc = need_point(c, 0, who, words)) ? rc : enter(c, FX_DEVICE, who);
     if ((rc = enter(c, FX_EVALUATES, who))) return rc;
@@ -73,26 +65,22 @@ static int logw_point_prologue(bioen_hip_ctx* c, const double* g, const double* 
 }
 
 // What the dense entries refuse, each with a message of its own: the frame is shared, an entry's reasons fill it
-struct DenseReasons {
-    const char *sharded, *panels, *product;
-};
-static const DenseReasons kGramReasons = {
+const DenseReasons kGramReasons = {
     "the all-gather of the segments' partial matrices is not built): use bioen_hip_forces_hessp there",
     "): use bioen_hip_forces_hessp there", "Gram product"};
-static const DenseReasons kColquadReasons = {
+const DenseReasons kColquadReasons = {
     "a rank holds its own structures' columns only and the entry does not gather the results)",
     " and a block cannot own all rows of its columns)", "quadratic form"};
-static const DenseReasons kNewtonReasons = {
+const DenseReasons kNewtonReasons = {
     "the Hessian pass is not built there): use the L-BFGS, or bioen_hip_forces_hessp with a host driver",
     " and there is no dense Hessian pass): use the L-BFGS there", "Gram product"};
-static const DenseReasons kLogwnReasons = {
+const DenseReasons kLogwnReasons = {
     "the all-gather of the segments' partial matrices is not built): use the L-BFGS there",
     " and there is no Gram pass over them): use the L-BFGS there", "Gram product"};
 
 // strip_blocks: the strip passes whose copy the entry reads -- the forces method's, or fwd_strip_blocks for the log-weights
 // entries
-static int dense_guard(const bioen_hip_ctx* c, const char* who, const DenseReasons& why,
-                       int (*strip_blocks)(const bioen_hip_ctx*) = forces_fused_blocks) {
+int dense_guard(const bioen_hip_ctx* c, const char* who, const DenseReasons& why, int (*strip_blocks)(const bioen_hip_ctx*)) {
     const std::string w(who);
     if (c->world != 1)
         return fail(BIOEN_HIP_ESTATE, (w + " is not served on a structure-sharded context (" + why.sharded).c_str());
@@ -108,7 +96,7 @@ static int dense_guard(const bioen_hip_ctx* c, const char* who, const DenseReaso
 }
 
 // A scratch buffer of the context (ctx.hpp: CtxScratch): allocated, zeroed, at its first use, kept until the context goes
-static int ensure_scratch(bioen_hip_ctx* c, int which, size_t doubles) {
+int ensure_scratch(bioen_hip_ctx* c, int which, size_t doubles) {
     CtxScratchBuf& s = c->scratch[which];
     if (s.p) return 0;
     if (int rc = dalloc_zero(&s.p, doubles, c->stream)) return rc;

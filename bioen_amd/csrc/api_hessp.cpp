@@ -1,16 +1,18 @@
-// Hessian-vector products of the log-weights objective (part of api.hip's translation unit: uses its static helpers;
-// kernels: kernels_hessp.hip; the mathematics: DESIGN section 6b).
+// Hessian-vector products of the log-weights objective (kernels: kernels_hessp.hip; the mathematics: DESIGN section 6b).
 //
 // A call with g != NULL is bioen_hip_logw_fdf with a gradient, after which the context keeps "the point": slot 0 holds e,
 // the gradient and the scalars, c->fixed the prior G, point_ybar the raw averages, point_fac every segment's softmax
 // factor.  A product at the kept point is then what a gradient costs: three N-vector sweeps around one forward and one
 // centred adjoint pass -- the context's own pass family, for up to kMaxBatch directions at once.
-// Whether a call sets the point or serves the kept one, and the refusal without one, is api_forces_point.inl's
-// logw_point_prologue, the dual Newton entries' too (api_logw_newton.inl).
+// Whether a call sets the point or serves the kept one, and the refusal without one, is api_forces_point.cpp's
+// logw_point_prologue, the dual Newton entries' too (api_logw_newton.cpp).
+#include <algorithm>
+
+#include "dense.hpp"
 
 namespace bioen {
 
-static int hessp_buffers(bioen_hip_ctx* c, int k) {
+int hessp_buffers(bioen_hip_ctx* c, int k) {
     int rc;
     if (!c->point_ybar && (rc = dalloc_zero(&c->point_ybar, (size_t)c->mp, c->stream))) return rc;
     if (!c->point_fac && (rc = dalloc_zero(&c->point_fac, (size_t)std::max(c->nseg, (int)kMaxSeg), c->stream))) return rc;
@@ -20,7 +22,7 @@ static int hessp_buffers(bioen_hip_ctx* c, int k) {
     return 0;
 }
 
-static void hessp_free(bioen_hip_ctx* c) {
+void hessp_free(bioen_hip_ctx* c) {
     double* bufs[] = {c->point_ybar, c->point_fac, c->hp_scal, c->fpoint_ybar, c->fpoint_rs, c->fpoint_q};
     for (double* b : bufs)
         if (b) (void)hipFree(b);
@@ -91,6 +93,8 @@ static int hessp_products(bioen_hip_ctx* c, int k, const double* v, double* hv) 
 
 }  // namespace bioen
 
+using namespace bioen;
+
 extern "C" int bioen_hip_logw_hessp(bioen_hip_ctx* c, const double* g, const double* G, double theta, int k,
                                     const double* v, double* hv, double* f, double* grad) {
     if (int rc = enter(c, FX_NONE, __func__)) return rc;      // a call rejected below leaves the point (and the device) alone ...
@@ -98,7 +102,7 @@ extern "C" int bioen_hip_logw_hessp(bioen_hip_ctx* c, const double* g, const dou
     if (k > 0 && (!v || !hv)) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     if (g && !G) return fail(BIOEN_HIP_EINVAL, "g without G");
     int rc;
-    // ONE point per context, of either method (api_forces_point.inl) ... with g it is an evaluation
+    // ONE point per context, of either method (api_forces_point.cpp) ... with g it is an evaluation
     if ((rc = logw_point_prologue(c, g, G, theta, 0, f, grad, __func__))) return rc;
     if (k == 0) return 0;
     rc = hessp_products(c, k, v, hv);

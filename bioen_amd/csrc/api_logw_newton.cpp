@@ -1,11 +1,14 @@
-// The log-weights method's dual Newton minimizer and the covariance it is built on (part of api.hip's translation unit: uses
-// its static helpers; kernels: kernels_logw_newton.hip).  N unknowns through an M x M system: C of the kept
-// log-weights point from k_logw_gram, C + theta I factorised and solved by section 6h's kernels (api_forces_newton.inl:
-// fnewton_factor, launch_fnewton_solve), the step from ONE centred adjoint pass on r + z.  Every N-vector stays in HBM; the
+// The log-weights method's dual Newton minimizer and the covariance it is built on (kernels: kernels_logw_newton.hip; DESIGN
+// section 6j).  N unknowns through an M x M system: C of the kept log-weights point from k_logw_gram, C + theta I
+// factorised and solved by section 6h's kernels (api_forces_newton.cpp: fnewton_factor, launch_fnewton_solve), the step from ONE centred adjoint pass on r + z.  Every N-vector stays in HBM; the
 // loop is log_weights.py's dual_newton_bioen_log_posterior_base, decision for decision.  DESIGN section 6k: C may come from
 // k_logw_gram_bf16 instead (split-BF16 products; -b, the gradient and every test of the loop stay FP64), and the loop runs a
 // whole theta series behind one call (bioen_logwn_series), warm- or cold-started.  The point is bioen_hip_logw_hessp's:
-// set, kept and refused by api_forces_point.inl's logw_point_prologue / logw_keep_point, the entries guarded by its dense_guard.
+// set, kept and refused by api_forces_point.cpp's logw_point_prologue / logw_keep_point, the entries guarded by its dense_guard.
+#include <cmath>
+#include <string>
+
+#include "dense.hpp"
 
 namespace bioen {
 
@@ -205,6 +208,8 @@ static int logwn_loop(bioen_hip_ctx* c, double theta, const bioen_logwn_config* 
 }
 
 }  // namespace bioen
+
+using namespace bioen;
 
 extern "C" int bioen_logwn_cov(bioen_hip_ctx* c, const double* g, const double* G, double theta, double* C, double* f,
                                double* grad) {

@@ -72,9 +72,7 @@ struct ForcesBatchEngine {
     ForcesBatchEngine(bioen_hip_ctx* ctx, const bioen_lbfgs_config& config, bool verb)
         : c(ctx), cfg(config), verbose(verb) {
         const size_t cnt = (size_t)c->mp * kMaxBatch;
-        if (!c->host_m)
-            note(hipHostMalloc(reinterpret_cast<void**>(&c->host_m), 2 * cnt * sizeof(double), hipHostMallocDefault),
-                 "hipHostMalloc");
+        note(forces_staging(c));
         um_h = c->host_m;
         gm_h = c->host_m ? c->host_m + cnt : nullptr;
         // results published by a kernel into a coherent host page (see k_forces_publish); BIOEN_HIP_FORCES_LIVE=0 or a

@@ -1,7 +1,10 @@
-// The host side's internal interface: what the translation units behind the C ABI (api.hip, comm.cpp) call across their
-// boundary, and nothing more.  Everything here is hidden: none of it is a dynamic symbol of the library.  A part of api.hip's
-// unit (an .inl file) becomes a translation unit of its own by including this header instead of api.hip's static helpers;
-// what it needs beyond these names is declared here first.
+// The host side's internal interface: what the translation units behind the C ABI call across their boundaries, and nothing
+// more -- api.hip (contexts, evaluations, the engines and the multimin drivers), comm.cpp (the exchange), and the
+// second-order and session entries, one unit each: api_hessp.cpp, api_forces_*.cpp, api_logw_newton.cpp, api_bfgs.cpp (what
+// those share among themselves is dense.hpp).  Everything here is hidden: none of it is a dynamic symbol of the library,
+// and the link refuses a name declared here that no unit defines.  What is still part of api.hip's unit (the engine_*.inl
+// files, api_multimin.inl) becomes a translation unit of its own by including this header instead of api.hip's static
+// helpers; what it needs beyond these names is declared here first.
 #pragma once
 
 #include <chrono>
@@ -39,6 +42,54 @@ enum : unsigned {
 };
 
 int enter(const bioen_hip_ctx* ctx, unsigned fx, const char* who);
+
+// ---- point and session (point_drop: api.hip; hessp_free: api_hessp.cpp; bfgs_free: api_bfgs.cpp) ---------------------------
+// The point a Hessian-vector product refers to is gone; `by`: an entry's name, or what failed
+void point_drop(bioen_hip_ctx* c, const char* by);
+void hessp_free(bioen_hip_ctx* c);        // the buffers of the kept point and of the products on it; the point with them
+void bfgs_free(bioen_hip_ctx* c);         // the dense inverse-Hessian BFGS session, if one is live (BfgsSession: api_bfgs.cpp only)
+
+// ---- allocation and transfers (api.hip) -------------------------------------------------------------------------------------
+int dalloc_zero(double** p, size_t count, hipStream_t s);      // count doubles on the device, zeroed on s
+// the pinned staging buffer of the forces method, c->host_m (2 x mp x kMaxBatch doubles: forces up | gradients down), on first need
+int forces_staging(bioen_hip_ctx* c);
+// Copies between the device and a CALLER's (pageable) buffer, on the context's stream: directly, or, where the runtime
+// refuses to pin the buffer, through pinned staging buffers of the library's own (the device-to-host forms are synchronous then)
+int h2d_user(bioen_hip_ctx* c, void* dst, const void* src, size_t bytes);
+hipError_t d2h_user(hipStream_t stream, void* dst, const void* src, size_t bytes);
+hipError_t d2h_user_2d(hipStream_t stream, char* dst, size_t dpitch, const char* src, size_t spitch, size_t width, size_t height);
+// host N-vectors are always GLOBAL (n_global long); a sharded context takes its slice
+int upload_n(bioen_hip_ctx* c, double* dst, const double* src);
+// gather a sharded device N-vector into a GLOBAL host vector (world == 1: plain download)
+int download_n(bioen_hip_ctx* c, double* dst_global, const double* src_local);
+// the scalars of the first nslots slots -> c->host_scal, synchronised; scalars behind a failed exchange are not results
+int read_scalars(bioen_hip_ctx* c, int nslots = 1);
+
+// ---- launch check (api.hip) -------------------------------------------------------------------------------------------------
+int check_launch();                       // hipGetLastError behind a run of kernel launches -> 0 | BIOEN_HIP_EHIP
+
+// ---- log-weights evaluation (api.hip; all asynchronous on c->stream) --------------------------------------------------------
+struct Round;                             // kernels.hpp
+// the round of the k problems in `slots`: their vectors, scalars and partials, stp and theta (NULL: zeros)
+Round make_round(bioen_hip_ctx* c, const int* slots, int k, const double* stp, const double* theta);
+// The pass family of a product with the matrix on the log-weights side, decided and made ready: *nblk > 0, the strip kernels
+// (with `colsum` the column-sum order copy too), or *nblk = 0, the streaming kernels on the row-major matrix.
+// strips_ok = false: the caller has reasons of its own against the strips.
+int choose_logw_passes(bioen_hip_ctx* c, bool strips_ok, int method, bool colsum, int* nblk);
+// r.x must hold the points and P_MAX their block maxima (launch_trial does both)
+int enqueue_logw_eval(bioen_hip_ctx* c, const Round& r, bool with_grad);
+// second half of an evaluation; needs w, scal[S_P] and the compact ybar_c / r_c of the SAME round still in place
+int enqueue_logw_adjoint(bioen_hip_ctx* c, const Round& r);
+// One evaluation of the round's single point, start to finish; keep_point: and what the Hessian-vector products keep of it.
+// -> *f; grad_out (a caller's global N-vector) if given; the round's scalars in host_scal
+int eval_logw_point(bioen_hip_ctx* c, const Round& r, bool with_grad, bool keep_point, double* f, double* grad_out);
+
+// ---- forces evaluation (api.hip) --------------------------------------------------------------------------------------------
+// what the forces method refuses on this context: a sharded one without canonical segments (strip_path_ok = false: without
+// exception), the affine model or anything but the strip passes on the reduced-storage experiment's copies
+int forces_guard(const bioen_hip_ctx* c, bool strip_path_ok = true);
+// k evaluations that share every matrix pass (slots 0 .. k-1); forces [k][m], grad [k][m]
+int forces_eval(bioen_hip_ctx* c, int k, const double* forces, const double* w0, const double* thetas, double* f, double* grad);
 
 // ---- the exchange interface (comm.cpp) ------------------------------------------------------------------------------------
 // One in-place all-gather of an exchange stage ([world][payload] doubles).  world == 1: nothing.  Three transports, in

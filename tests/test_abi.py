@@ -58,6 +58,19 @@ def test_only_the_abi_is_exported_under_c_names():
     assert not stray, "exported under C names without being part of the ABI: %s" % stray
 
 
+def test_library_imports_nothing_of_its_own():
+    """the host side is several translation units that call each other through csrc/host.hpp and csrc/dense.hpp; a shared
+    library links with such a call left undefined and fails only when it is loaded (or, lazily bound, when it is
+    called).  No undefined dynamic symbol may carry the project's name, mangled (N5bioen...) or plain (bioen_...): what
+    the library needs of itself it defines."""
+    from bioen_amd import _lib
+    out = subprocess.check_output(["nm", "-D", "--undefined-only", _lib.LIB_PATH]).decode()
+    undefined = [line.split()[-1] for line in out.splitlines() if line.strip()]
+    assert undefined, "nm listed no imports at all (the HIP runtime's are expected): is this the library?"
+    own = sorted(n for n in undefined if "bioen" in n)
+    assert not own, "left undefined in the library: %s" % own
+
+
 def test_struct_layouts_match_the_reference_packing():
     from bioen_amd import _lib
     # lbfgs_config_params of c_bioen_common.h:69-79: int,int,5 doubles,int,int -> 56 bytes on LP64

@@ -1,5 +1,5 @@
 """GPU tests of the dense inverse-Hessian BFGS (scipy's fmin_bfgs with H in HBM: bioen_amd/bfgs.py,
-csrc/kernels_bfgs.hip, csrc/api_bfgs.inl): H against a host recurrence on the device's own steps, the HBM regime,
+csrc/kernels_bfgs.hip, csrc/api_bfgs.cpp): H against a host recurrence on the device's own steps, the HBM regime,
 parity with today's host fmin_bfgs on the device objective and with the reference's converged optimum, determinism,
 footprint and limits, and the public API's opt-in."""
 import warnings

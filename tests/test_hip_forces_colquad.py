@@ -1,5 +1,5 @@
 """GPU tests of the per-structure quadratic forms a_j^T P a_j at a kept forces point (csrc/kernels_forces_colquad.hip,
-csrc/api_forces_colquad.inl, Context.forces_colquad) and of forces.laplace_error_bars on the device: every result against
+csrc/api_forces_colquad.cpp, Context.forces_colquad) and of forces.laplace_error_bars on the device: every result against
 the formula in numpy.longdouble for four kinds of P, the bitwise invariants, the affine model, the state rules and
 refusals, the footprint, and the error bars at a converged optimum against the numpy restatements."""
 import numpy as np

@@ -1,6 +1,6 @@
 """GPU tests of the forces method's dense kernels WHERE THEIR LOOPS RUN LONG (csrc/fgram.hpp: fgram_pass / fgram16_pass at the
-forces point, csrc/kernels_forces_gram.hip: k_fgram_sum_sets, csrc/kernels_forces_colquad.hip, csrc/api_forces_laplace.inl,
-csrc/api_forces_newton.inl): Context.forces_gram, forces_gram_bf16, forces_colquad, forces_laplace and opt_newton_forces at
+forces point, csrc/kernels_forces_gram.hip: k_fgram_sum_sets, csrc/kernels_forces_colquad.hip, csrc/api_forces_laplace.cpp,
+csrc/api_forces_newton.cpp): Context.forces_gram, forces_gram_bf16, forces_colquad, forces_laplace and opt_newton_forces at
 the shapes of tests/test_hip_strip_loops.py's REGIMES at which a set chains 16 ... 132 strips, a block of the quadratic-form
 pass runs 4 ... 17 panels, and the sum of the sets meets more than eight groups on eight segments.  The ordinary test files
 of these entries reach chains of 7 and a block's second panel.  tests/README_forces_dense_loops.md has the regime table, the

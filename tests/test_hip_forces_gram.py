@@ -1,5 +1,5 @@
 """GPU tests of the dense Hessian and the covariance of the forces objective in one pass (csrc/kernels_forces_gram.hip,
-csrc/api_forces_gram.inl, Context.forces_gram): every entry against the Hessian the products build at the same kept point
+csrc/api_forces_gram.cpp, Context.forces_gram): every entry against the Hessian the products build at the same kept point
 (Context.forces_hessian, the device oracle) and against the formula in numpy.longdouble, the bitwise invariants, the
 affine model, the state rules and refusals, and scipy's trust-exact fed by it through find_optimum."""
 from concurrent.futures import ThreadPoolExecutor

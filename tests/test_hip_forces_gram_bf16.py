@@ -1,5 +1,5 @@
 """GPU tests of the forces Hessian from split-BF16 operands (csrc/kernels_forces_gram.hip: k_forces_gram_bf16,
-csrc/api_forces_gram.inl, Context.forces_gram_bf16): every entry against the FP64 pass at the same kept point
+csrc/api_forces_gram.cpp, Context.forces_gram_bf16): every entry against the FP64 pass at the same kept point
 (Context.forces_gram) and against the numpy restatement with the same rounding points, the bitwise invariants, the affine
 model, the state rules and refusals, the footprint, and scipy's trust-exact fed by it through find_optimum."""
 import numpy as np

@@ -1,5 +1,5 @@
 """GPU tests of the Hessian-vector products of the forces objective (csrc/kernels_forces_hessp.hip, the SM_TANGENT /
-SM_PRODUCT forms of k_strip and k_strip2, csrc/api_forces_hessp.inl, Context.forces_hessp / forces_hessian) and of scipy's
+SM_PRODUCT forms of k_strip and k_strip2, csrc/api_forces_hessp.cpp, Context.forces_hessp / forces_hessian) and of scipy's
 trust-exact on the device objective: the product against an independent extended-precision evaluation of the formula, the
 strip loops with several strips per slot and segment, the affine model, the bitwise invariants, the one-point-per-context
 state rules, the launch counts behind "a product costs a gradient", and the driver through find_optimum."""

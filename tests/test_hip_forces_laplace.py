@@ -1,4 +1,4 @@
-"""GPU tests of the Laplace error bars formed on the device (csrc/kernels_forces_laplace.hip, csrc/api_forces_laplace.inl,
+"""GPU tests of the Laplace error bars formed on the device (csrc/kernels_forces_laplace.hip, csrc/api_forces_laplace.cpp,
 Context.forces_inverse / forces_laplace, forces.laplace_error_bars(on_device=True)): the inverse from the
 resident Cholesky factor against LAPACK on caller matrices, its bitwise invariants, pivot failures as ordinary results, the
 whole entry against the host path at converged optima, the affine model, the kept-point rules, the refusals."""

@@ -1,5 +1,5 @@
 """GPU tests of the forces method's device-resident Newton minimizer (csrc/kernels_forces_newton.hip,
-csrc/api_forces_newton.inl, Context.forces_newton_factor / forces_newton_solve / opt_newton_forces):
+csrc/api_forces_newton.cpp, Context.forces_newton_factor / forces_newton_solve / opt_newton_forces):
 the Cholesky factorisation and the solves against LAPACK on caller matrices, pivot failures as ordinary results, the
 bitwise invariants, the state rules and refusals, and the loop through find_optimum against its numpy restatement."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""GPU tests of the Hessian-vector products of the log-weights objective (csrc/kernels_hessp.hip, csrc/api_hessp.inl,
+"""GPU tests of the Hessian-vector products of the log-weights objective (csrc/kernels_hessp.hip, csrc/api_hessp.cpp,
 Context.logw_hessp) and of scipy's Newton-CG drivers on the device objective: the product against an independent
 extended-precision evaluation of the formula on every pass family, the bitwise invariants, the point's state rule, the
 launch counts behind "a product costs a gradient", eight thread-ranks, and the drivers through find_optimum."""

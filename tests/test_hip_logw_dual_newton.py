@@ -1,4 +1,4 @@
-"""GPU tests of the log-weights method's dual Newton minimizer (csrc/kernels_logw_newton.hip, csrc/api_logw_newton.inl,
+"""GPU tests of the log-weights method's dual Newton minimizer (csrc/kernels_logw_newton.hip, csrc/api_logw_newton.cpp,
 Context.logw_cov / opt_dual_newton_logw): the covariance pass against the centred formula in
 numpy.longdouble on the geometry list of tests/test_hip_forces_gram.py and against forces_gram's C for the same weights, its
 bitwise invariants, canonical segments and the affine model; the loop through find_optimum against its numpy restatement;

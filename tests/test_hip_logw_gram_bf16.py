@@ -1,5 +1,5 @@
 """GPU tests of the log-weights theta series by dual Newton on a split-BF16 covariance (csrc/kernels_logw_newton.hip:
-k_logw_gram_bf16; csrc/api_logw_newton.inl: bioen_logwn_cov_bf16, bioen_logwn_series; Context.logw_cov_bf16,
+k_logw_gram_bf16; csrc/api_logw_newton.cpp: bioen_logwn_cov_bf16, bioen_logwn_series; Context.logw_cov_bf16,
 opt_dual_newton_logw_series).
 
 Tolerances of the pass, derived and not tuned.  With a = Y' - centre (the affine model: its scaled rows), G' = sum_j w_j a_j

@@ -1,4 +1,4 @@
-"""GPU tests of the log-weights dual Newton minimizer (csrc/kernels_logw_newton.hip, csrc/api_logw_newton.inl,
+"""GPU tests of the log-weights dual Newton minimizer (csrc/kernels_logw_newton.hip, csrc/api_logw_newton.cpp,
 Context.opt_dual_newton_logw) WHERE ITS LOOPS RUN LONG and in the regimes the five small fixtures of
 tests/test_hip_logw_dual_newton.py never enter:
 

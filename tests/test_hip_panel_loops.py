@@ -1,5 +1,5 @@
 """GPU tests of the ROW-PANEL passes (M > 1024: strip.hpp's panels of 1024 rows; csrc/strip_plan.cpp: launch_fwd_strip /
-launch_adj_strip over the panel list, api.hip: enqueue_forces_eval with psets > 0, api_forces_hessp.inl's panel path) where
+launch_adj_strip over the panel list, api.hip: enqueue_forces_eval with psets > 0, api_forces_hessp.cpp's panel path) where
 ONE BLOCK SLOT RUNS SEVERAL STRIPS OF A COLUMN SEGMENT -- tests/test_hip_strip_loops.py's question for the other pass family.
 At eight segments the forward plan on panels is 32 groups per segment, so up to N = 4096 a slot runs one strip, one chunk;
 every other file's M > 1024 shapes stay below that or have two panels and tc = 1.  What is new here:
@@ -10,7 +10,7 @@ every other file's M > 1024 shapes stay below that or have two panels and tc = 1
                              one-copy form (k_strip / k_strip2 ADJ, 256 groups of 264 resp. 568 strips per segment)
   the forces panel passes    k_forces_seg_exp / k_forces_seg_t with seg_sets = gs * nch unfolded (a rank of eight, a
                              one-segment context), the per-segment softmax merge with segments whose maxima all differ
-  the forces products        api_forces_hessp.inl's four passes with k_fhp_seg_t on the same sets
+  the forces products        api_forces_hessp.cpp's four passes with k_fhp_seg_t on the same sets
   canonical order            "the GPU count changes no bit" on panels where a chunk is more than one strip
   the panel limit            16 panels (M = 16384: the last the strip kernels serve) and 17 (the streaming kernels)
 
