@@ -203,6 +203,7 @@ _SIGNATURES = {
     "bioen_logwn_cov_bf16": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp]),
     "bioen_logwn_series": (C.c_int, [ctx_p, dp, dp, dp, C.c_int, C.POINTER(LogwNewtonConfig), C.c_int, C.c_int, dp,
                                      C.POINTER(LogwNewtonSeriesResult)]),
+    "bioen_logwn_laplace": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip, dp, dp]),
 }
 
 _lib = None
@@ -691,6 +692,67 @@ class Context(object):
         check(lib().bioen_logwn_opt(self._h, ptr(g0), ptr(G), float(theta), C.byref(cfg), ptr(out), C.byref(res)))
         return dict(g=out, status=res.status, fmin=res.fmin, gmax=res.gmax, wmax=res.wmax, iterations=res.iterations,
                     evaluations=res.evaluations, factorisations=res.factorisations)
+
+    def logw_laplace(self, g=None, G=None, theta=None, observables=None, matrices=True, vectors=True):
+        """The Laplace error bars at a log-weights point, formed on the device (bioen_logwn_laplace; M <= 1024):
+        C from logw_cov's pass, C + theta I factorised and inverted in HBM, the inverse handed to forces_colquad's pass
+        where it stands.  With `g` (and G) the point is evaluated first, as by logw_cov, and kept; without, the kept
+        log-weights point is served -- right after opt_dual_newton_logw at no further evaluation -- (BioenHipError as
+        logw_hessp raises it).  theta > 0 is required either way.  -> dict: info (LAPACK dpotrf's; != 0: every array below
+        is None and logdet, min_pivot are nan), logdet = ln det (C + theta I), min_pivot, std_averages (m,), cov_averages
+        ((m, m), bitwise symmetric; None with matrices=False), w, leverage, var_logw, std_w ((n,) each; None with
+        vectors=False, and the pass over the matrix does not run), and with g also f and grad.  `observables`, (n,) or
+        (k, n): per-structure quantities that were not fitted; obs_averages and var_observables, (k,), are their refined
+        averages and the variances of those (more than 8 are served in chunks of 8 at the kept point).  A single weight is
+        poorly determined whenever theta w_j << 1 (std_w_j / w_j ~ 1 / sqrt(theta w_j)): read the averages."""
+        if theta is None:
+            raise ValueError("logw_laplace needs theta")
+        if g is not None and G is None:
+            raise ValueError("logw_laplace with g needs G")
+        m, n = self.m, self.n
+        obs = None
+        if observables is not None:
+            obs = as_f64(observables)
+            if obs.ndim == 1:
+                obs = obs.reshape(1, -1)
+            if obs.ndim != 2 or obs.shape[1] != n or obs.shape[0] < 1:
+                raise ValueError("observables must be (N,) or (k, N) with N = %d, got %s" % (n, (np.shape(observables),)))
+        kobs = 0 if obs is None else obs.shape[0]
+        sa = np.empty(m)
+        ca = np.empty((m, m)) if matrices else None
+        vecs = [np.empty(n) if vectors else None for _ in range(4)]
+        oa, vo = (np.empty(kobs), np.empty(kobs)) if kobs else (None, None)
+        logdet, pivot, info = C.c_double(float("nan")), C.c_double(float("nan")), C.c_int(0)
+        fn = lib().bioen_logwn_laplace
+
+        def chunk(k0):
+            k = min(8, kobs - k0)
+            return (ptr(obs[k0:k0 + k]), k, ptr(oa[k0:k0 + k]), ptr(vo[k0:k0 + k])) if k > 0 else (None, 0, None, None)
+
+        po, k, pa, pv = chunk(0)
+        out = [ptr(a) if a is not None else None for a in [sa, ca] + vecs] + [pa, pv, C.byref(logdet), C.byref(pivot),
+                                                                                C.byref(info)]
+        res = {}
+        if g is None:
+            check(fn(self._h, None, None, float(theta), po, k, *(out + [None, None])))
+        else:
+            g, G, f, grad = self._point("N", ("g", "G"), g, G)
+            check(fn(self._h, ptr(g), ptr(G), float(theta), po, k, *(out + [C.byref(f), ptr(grad)])))
+            res.update(f=f.value, grad=grad)
+        for k0 in range(8, kobs if info.value == 0 else 0, 8):      # the rest at the kept point: the observables' path alone
+            po, k, pa, pv = chunk(k0)
+            more = C.c_int(0)
+            check(fn(self._h, None, None, float(theta), po, k, None, None, None, None, None, None, pa, pv, None, None,
+                     C.byref(more), None, None))
+            if more.value:
+                info.value = more.value
+        ok = info.value == 0
+        res.update(info=info.value, logdet=logdet.value if ok else float("nan"), min_pivot=pivot.value if ok else float("nan"),
+                   std_averages=sa if ok else None, cov_averages=ca if ok else None)
+        res.update(zip(("w", "leverage", "var_logw", "std_w"), (v if ok else None for v in vecs)))
+        if kobs:
+            res.update(obs_averages=oa if ok else None, var_observables=vo if ok else None)
+        return res
 
     def logw_cov_bf16(self, g=None, G=None, theta=None, cov=True):
         """logw_cov with the M x M x N product from split-BF16 operands on the BF16 matrix cores (bioen_logwn_cov_bf16;

@@ -17,13 +17,8 @@ static const DenseReasons kLaplaceReasons = {
 static const PointWords kLaplacePoint = {"call with forces",
                                          "set a forces point first (bioen_laplace_forces, bioen_hip_forces_gram with forces)"};
 
-struct FLaplaceBuf {
-    double *W, *Hi, *B, *Ca;      // L^-1 and W C (leading dimension ld); H^-1 and C H^-1 C (m x m, dense)
-    double *ldiag, *dg;           // diag L; diag H^-1, then (at dg + ld) diag C H^-1 C
-    int ld;
-};
-
-static FLaplaceBuf flaplace_layout(const bioen_hip_ctx* c) {
+// (FLaplaceBuf: dense.hpp -- here W = L^-1, B = W C, Hi = H^-1, Ca = C H^-1 C; the log-weights error bars share the buffer)
+FLaplaceBuf flaplace_layout(const bioen_hip_ctx* c) {
     FLaplaceBuf b{};
     const size_t mp = (size_t)c->mp;
     b.ld = c->mp;
@@ -36,7 +31,7 @@ static FLaplaceBuf flaplace_layout(const bioen_hip_ctx* c) {
     return b;
 }
 
-static int flaplace_buffers(bioen_hip_ctx* c) {
+int flaplace_buffers(bioen_hip_ctx* c) {
     const size_t mp = (size_t)c->mp;
     return ensure_scratch(c, SCRATCH_LAPLACE, 4 * mp * mp + 3 * mp);
 }
@@ -67,9 +62,10 @@ static int flaplace_gram(bioen_hip_ctx* c, const double** cov, const double** he
 }
 
 // ln det H = 2 sum_i ln L_ii, in index order; min_i L_ii^2
-static void flaplace_logdet(const std::vector<double>& ldiag, double* logdet, double* min_pivot) {
-    double s = 0.0, lo = ldiag.empty() ? 0.0 : ldiag[0];
-    for (double v : ldiag) {
+void flaplace_logdet(const double* ldiag, int m, double* logdet, double* min_pivot) {
+    double s = 0.0, lo = m > 0 ? ldiag[0] : 0.0;
+    for (int i = 0; i < m; ++i) {
+        const double v = ldiag[i];
         s += std::log(v);
         lo = std::min(lo, v);
     }
@@ -97,7 +93,7 @@ extern "C" int bioen_laplace_forces_inverse(bioen_hip_ctx* c, const double* A, d
     }
     std::vector<double> ldiag;
     if ((rc = flaplace_inverse(c, src, info, ldiag)) || *info) return rc;
-    flaplace_logdet(ldiag, logdet, nullptr);
+    flaplace_logdet(ldiag.data(), c->m, logdet, nullptr);
     if (Ainv) {
         BIOEN_HIP_CHECK(d2h_user(c->stream, Ainv, flaplace_layout(c).Hi, (size_t)c->m * c->m * sizeof(double)));
         BIOEN_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -119,7 +115,7 @@ extern "C" int bioen_laplace_forces(bioen_hip_ctx* c, const double* forces, cons
     if ((rc = flaplace_gram(c, &cov, &hess))) return rc;
     std::vector<double> ldiag;
     if ((rc = flaplace_inverse(c, hess, info, ldiag)) || *info) return rc;
-    flaplace_logdet(ldiag, logdet, min_pivot);
+    flaplace_logdet(ldiag.data(), c->m, logdet, min_pivot);
     const FLaplaceBuf b = flaplace_layout(c);
     const int m = c->m, mps = (int)round_up((size_t)c->m, 16);      // the strips' rows (M <= 1024: one panel)
     const size_t pcount = (size_t)mps * mps, mbytes = (size_t)m * sizeof(double);

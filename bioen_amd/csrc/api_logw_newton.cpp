@@ -12,11 +12,11 @@
 
 namespace bioen {
 
-static const PointWords kLogwnPoint = {"call with g", "set a log-weights point first (bioen_logwn_cov or bioen_hip_logw_hessp with g)"};
+const PointWords kLogwnPoint = {"call with g", "set a log-weights point first (bioen_logwn_cov or bioen_hip_logw_hessp with g)"};
 
 // After a point's evaluation the guard once more (dense_guard, on the copy the log-weights forward pass reads): the strip
 // copies exist by now, or never will
-static int logwn_copies(const bioen_hip_ctx* c, const char* who) {
+int logwn_copies(const bioen_hip_ctx* c, const char* who) {
     if (int rc = dense_guard(c, who, kLogwnReasons, fwd_strip_blocks)) return rc;
     return c->Ys[0] ? 0 : fail(BIOEN_HIP_ESTATE, (std::string(who) + " needs the strip copies of the matrix").c_str());
 }
@@ -32,7 +32,7 @@ enum LogwnSource : int { LOGWN_FP64 = 0, LOGWN_BF16 = 1 };
 
 // C of the kept log-weights point into SCRATCH_LOGW_GRAM, not downloaded; negb (may be NULL): -Yc grad for the solve (the
 // same bits from either source)
-static int logwn_gram(bioen_hip_ctx* c, int source, const double** cov, double* negb) {
+int logwn_gram(bioen_hip_ctx* c, int source, const double** cov, double* negb) {
     int rc;
     const GramPlan p = logw_gram_plan(c);
     if ((rc = ensure_scratch(c, SCRATCH_LOGW_GRAM, p.doubles))) return rc;

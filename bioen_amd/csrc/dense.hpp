@@ -77,5 +77,24 @@ int fnewton_buffers(bioen_hip_ctx* c);
 // chol(lower(src) + lambda I) -> the context's L; *info as LAPACK's; dmax (may be NULL): max |diag src|
 int fnewton_factor(bioen_hip_ctx* c, const double* src, double lambda, int* info, double* dmax);
 
+// ---- from the factor to its inverse (api_forces_laplace.cpp) ----------------------------------------------------------------
+struct FLaplaceBuf {
+    double *W, *Hi, *B, *Ca;      // L^-1 and a work matrix (leading dimension ld); the inverse and a covariance (m x m, dense)
+    double *ldiag, *dg;           // diag L; diag of the inverse, then (at dg + ld) diag of the covariance
+    int ld;
+};
+FLaplaceBuf flaplace_layout(const bioen_hip_ctx* c);      // where the parts of SCRATCH_LAPLACE stand
+int flaplace_buffers(bioen_hip_ctx* c);
+// ln det = 2 sum_i ln L_ii, in index order; min_i L_ii^2 (either may be NULL); ldiag: m values on the host
+void flaplace_logdet(const double* ldiag, int m, double* logdet, double* min_pivot);
+
+// ---- the covariance of the kept log-weights point (api_logw_newton.cpp) -----------------------------------------------------
+extern const PointWords kLogwnPoint;      // the refusal without a log-weights point, as the bioen_logwn_* entries word it
+// after a point's evaluation the guard once more (the strip copies exist by now, or never will)
+int logwn_copies(const bioen_hip_ctx* c, const char* who);
+// C of the kept log-weights point into SCRATCH_LOGW_GRAM, not downloaded (source 0: the FP64 pass, 1: the split-BF16 one);
+// negb (may be NULL): -Yc grad
+int logwn_gram(bioen_hip_ctx* c, int source, const double** cov, double* negb);
+
 }  // namespace bioen
 #pragma GCC visibility pop

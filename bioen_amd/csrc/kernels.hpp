@@ -227,6 +227,22 @@ void launch_logwn_stats(bioen_hip_ctx* c, const double* x, const double* e, cons
 void launch_logwn_step(bioen_hip_ctx* c, const double* x, const double* cadj, const double* grad, const double* pscal,
                        double theta, double* u, double* out);
 
+// ---- the log-weights method's Laplace error bars at the kept point (kernels_logw_laplace.hip): what stands
+// between k_logw_gram, the factor, its inverse P = (C + theta I)^-1 and k_forces_colquad's pass ---------------------------
+// Ca (m x m, dense, bitwise symmetric) <- I - theta P; ybp [m] <- ybar - strip centre (k_forces_colquad's ybar')
+void launch_logwl_matrices(bioen_hip_ctx* c, const double* P, double theta, const double* ybar, double* Ca, double* ybp);
+// per structure, from e (w = e S_INV[segment]) and the quadratic forms q: w, leverage = w q, var ln w = (1 - w - w q) /
+// (theta w), std w = sqrt(max(w (1 - w - w q), 0) / theta) -- each ld doubles, a NULL one is not written
+void launch_logwl_finish(bioen_hip_ctx* c, const double* e, const double* q, const double* pscal, double theta, double* w,
+                         double* lev, double* vlw, double* sdw);
+// held-out observables o_a = h.v[a], behind launch_hessp_dots / launch_hessp_tangent (obar in S_SPARE0, t = e (o - obar)):
+void launch_logwl_obs_var(bioen_hip_ctx* c, const HesspArgs& h);       // block partials of sum e (o - obar)^2 -> X_GRAD
+// behind the forward pass on t: X [k][mp], keep [k][mp] <- c_a = S Y' t_a; sc [2 k] <- Var_w(o_a), obar_a
+void launch_logwl_obs_rhs(bioen_hip_ctx* c, const HesspArgs& h, double* X, double* keep, double* sc);
+// behind the solve X <- P X: out[a] <- obar_a, out[kMaxBatch + a] <- (Var_w(o_a) - keep_a . X_a) / theta
+void launch_logwl_obs_finish(bioen_hip_ctx* c, int k, double theta, const double* X, const double* keep, const double* sc,
+                             double* out);
+
 // ---- dense FP64 Cholesky factorisation and solves on the device, M <= 1024 (kernels_forces_newton.hip) --------
 constexpr int kFNewtonPanel = 64;           // columns of a panel: a diagonal tile is one wave's, a trailing tile four waves'
 // L (ldl x ldl, ldl >= m) <- chol(lower(src) + lambda I), src m x m with leading dimension lds; dg <- diag(src); *info as

@@ -459,6 +459,20 @@ def bioen_opt_dual_newton_logw_series(g, G, yTilde, YTilde, thetas, params):
     return [r["g"] for r in res], [r["fmin"] for r in res]
 
 
+def laplace_logw(g, G, yTilde, YTilde, theta, observables=None, matrices=True):
+    """-> (Context.logw_laplace's dict at the point (g, G, theta), C or None): the Laplace error bars of the log-weights
+    method formed on the device; with `matrices` the covariance of the observables comes from logw_cov at the
+    point the call has kept.  info != 0 is the caller's to judge (log_weights.laplace_error_bars raises ValueError)."""
+    ctx, cached = _context_for(yTilde, YTilde)
+    try:
+        r = ctx.logw_laplace(g=np.asarray(g, dtype=np.float64).reshape(-1), G=np.asarray(G, dtype=np.float64).reshape(-1),
+                             theta=theta, observables=observables, matrices=matrices)
+        C = ctx.logw_cov() if matrices and r["info"] == 0 else None
+    finally:
+        _release(ctx, cached)
+    return r, C
+
+
 def bioen_opt_newton_forces(forces, w0, yTilde, YTilde, theta, params):
     """-> (forces_opt[m], fmin): the device-resident Newton minimizer (Context.opt_newton_forces).  Status 0 (max|g| <=
     gtol) and 2 (at the minimum to the rounding of f) return; 1 (max_iterations) and 3 (the damping left its range) raise

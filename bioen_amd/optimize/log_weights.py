@@ -233,6 +233,85 @@ def dual_newton_step(p, yT, theta, C=None):
     return u, z
 
 
+# ------------------------------------------------------------------ Laplace error bars
+def laplace_error_bars(gPrime, G, y, yTilde, YTilde, theta, observables=None, use_c=True, matrices=True):
+    """Laplace error bars at log-weights `gPrime` (n,) -- an optimum of the log-weights objective -- from the Hessian
+    H~ = theta (W - w w^T) + W Yc^T Yc W of the dual Newton step, which is the exact Hessian at an optimum.  H~ 1 = 0 is
+    the gauge of the log-weights, so only gauge-invariant quantities have a posterior covariance; through Woodbury on the
+    M x M system the dual Newton solves, with w = softmax(gPrime), a_j = y_j - ybar, C = sum_j w_j a_j a_j^T and
+    P = inv(C + theta I):  -> dict
+
+      w (n,), C (m, m), logdet = ln det (C + theta I)
+      leverage (n,): w_j a_j^T P a_j, in [0, 1 - w_j) -- the share of structure j's prior log-weight variance the data removed
+      var_logw (n,): (1 - w_j - leverage_j) / (theta w_j) = (e_j - w)^T pinv(H~) (e_j - w), the variance of ln w_j
+      std_w (n,):    sqrt(w_j (1 - w_j - leverage_j) / theta)
+      cov_averages = C P = I - theta P, std_averages    (m, m), (m,)   of ybar in the units of yTilde
+      with `observables`, (n,) or (k, n) -- per-structure quantities o that were NOT fitted (a held-out data set, a radius
+      of gyration): obs_averages (k,) = sum_j w_j o_j, and std_observables (k,), the roots of
+      var(obar) = (Var_w(o) - c^T P c) / theta,  c = sum_j w_j (o_j - obar) a_j,  Var_w(o) = sum_j w_j (o_j - obar)^2
+
+    An individual weight is poorly determined whenever theta w_j << 1 (std_w_j / w_j ~ 1 / sqrt(theta w_j)): the
+    information is in the averages and the held-out averages.  cov_averages coincides with forces.laplace_error_bars' at the
+    shared optimum (H = theta C + C C there).
+
+    use_c: one Context.logw_laplace call on a resident context (M <= 1024), plus logw_cov at the kept point
+    for C; with matrices=False C and cov_averages are None and nothing of size m^2 is downloaded.  Else the numpy
+    restatement, the specification: the closed forms above with np.linalg.cholesky.  ValueError if theta <= 0 or the
+    factorisation fails (a point that is not finite).  `G` enters only the device's evaluation of the point; `y` unused."""
+    g = np.asarray(gPrime, dtype=np.float64).reshape(-1)
+    theta = float(theta)
+    if not (theta > 0.0 and np.isfinite(theta)):
+        raise ValueError("laplace_error_bars needs theta > 0 (the error bars divide by theta), got %r" % theta)
+    obs = None
+    if observables is not None:
+        obs = np.asarray(observables, dtype=np.float64)
+        obs = obs.reshape(1, -1) if obs.ndim == 1 else obs
+        if obs.ndim != 2 or obs.shape[1] != g.size or obs.shape[0] < 1:
+            raise ValueError("observables must be (n,) or (k, n) with n = %d, got %s" % (g.size, (np.shape(observables),)))
+    if use_c:
+        r, C = c_bioen.laplace_logw(g, G, yTilde, YTilde, theta, obs, matrices)
+        if r["info"] != 0:
+            raise ValueError("laplace_error_bars: C + theta I did not factorise (the device factorisation ended at pivot "
+                             "%d): the point is not finite" % r["info"])
+        out = {"w": r["w"], "C": C, "cov_averages": r["cov_averages"], "std_averages": r["std_averages"],
+               "leverage": r["leverage"], "var_logw": r["var_logw"], "std_w": r["std_w"], "logdet": r["logdet"]}
+        if obs is not None:
+            out.update(obs_averages=r["obs_averages"], std_observables=np.sqrt(np.maximum(r["var_observables"], 0.0)))
+        return out
+    import scipy.linalg
+    yT = np.asarray(yTilde, dtype=np.float64)
+    if not np.isfinite(g).all():
+        raise ValueError("laplace_error_bars: the point is not finite")
+    e = np.exp(g - g.max())
+    w = e / e.sum()
+    A = yT - yT.dot(w)[:, None]
+    C = (A * w).dot(A.T)
+    C = np.tril(C) + np.tril(C, -1).T
+    m = C.shape[0]
+    try:
+        L = np.linalg.cholesky(C + theta * np.eye(m))
+    except np.linalg.LinAlgError:
+        raise ValueError("laplace_error_bars: C + theta I did not factorise: the point is not finite")
+    P = scipy.linalg.cho_solve((L, True), np.eye(m))
+    P = 0.5 * (P + P.T)
+    leverage = w * np.einsum("ij,ij->j", A, P.dot(A))
+    rest = (1.0 - w) - leverage
+    cov_av = np.eye(m) - theta * P
+    out = {"w": w, "C": C, "cov_averages": cov_av, "std_averages": np.sqrt(np.maximum(np.diag(cov_av), 0.0)),
+           "leverage": leverage, "var_logw": rest / (theta * w), "std_w": np.sqrt(np.maximum(w * rest, 0.0) / theta),
+           "logdet": 2.0 * float(np.log(np.diag(L)).sum())}
+    if obs is not None:
+        obar = obs.dot(w)
+        d = obs - obar[:, None]
+        var_w = (d * d).dot(w)
+        c = (d * w).dot(A.T)                                   # (k, m)
+        var = (var_w - np.einsum("ki,ki->k", c, scipy.linalg.cho_solve((L, True), c.T).T)) / theta
+        out.update(obs_averages=obar, std_observables=np.sqrt(np.maximum(var, 0.0)))
+    if not matrices:
+        out.update(C=None, cov_averages=None)
+    return out
+
+
 _DUAL_NEWTON_SOURCES = ("gram", "gram_bf16")
 
 

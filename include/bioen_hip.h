@@ -776,6 +776,41 @@ int bioen_logwn_series(bioen_hip_ctx* ctx, const double* g0, const double* G, co
                        const bioen_logwn_config* config, int source, int warm, double* gopt,
                        bioen_logwn_series_result* results);
 
+/* ---- log-weights method: Laplace error bars at a log-weights point, formed on the device.  DESIGN section 6l.  With
+ * w = softmax(g), a_j = y_j - ybar, C = sum_j w_j a_j a_j^T (bioen_logwn_cov's) and P = (C + theta I)^-1, the
+ * gauge-invariant quantities of the posterior's Gaussian approximation -- the Hessian theta (W - w w^T) + W Yc^T Yc W of
+ * DESIGN 6j, which is the exact one at an optimum -- through the M x M system the dual Newton solves:
+ *   leverage_j = w_j a_j^T P a_j, in [0, 1 - w_j)      var(ln w_j) = (1 - w_j - leverage_j) / (theta w_j)
+ *   cov_averages = C P = I - theta P                   var(obar)   = (Var_w(o) - c^T P c) / theta, c = sum_j w_j (o_j - obar) a_j
+ * The refusals (BIOEN_HIP_ESTATE) are bioen_logwn_cov's. ---- */
+
+/* The error bars at a log-weights point.  The point is bioen_logwn_cov's: with g [n] (and G [n]) it is evaluated and kept
+ * (*f and grad [n], either may be NULL, are bioen_hip_logw_fdf's bits; a BFGS session ends); with g == NULL the kept
+ * log-weights point is served -- right after bioen_logwn_opt without a further evaluation -- (BIOEN_HIP_ESTATE without
+ * one; point and session stay; G, f and grad are ignored).  theta is used as given in both cases.  Every output may be
+ * NULL, and only what is asked for is computed and downloaded:
+ *   std_averages [m], cov_averages [m x m]   the posterior covariance of the refined averages (units of yTilde; affine
+ *                                            model: of the effective observables), bitwise symmetric, and the roots of
+ *                                            its diagonal
+ *   w [n], leverage [n]                      the weights; the share of structure j's prior log-weight variance the data removed
+ *   var_logw [n], std_w [n]                  the variance of ln w_j and the standard deviation of w_j.
+ *                                            An individual weight is poorly determined whenever theta w_j << 1 (std_w_j /
+ *                                            w_j ~ 1 / sqrt(theta w_j)): the information is in the averages, above and below.
+ *                                            Without any of these four the quadratic-form pass over the matrix does not run.
+ *   observables [nobs][n], nobs <= 8         per-structure quantities that were NOT fitted (both or neither):
+ *   obs_averages [nobs], var_observables [nobs]   their refined averages sum_j w_j o_j and the variances of those
+ *   *logdet, *min_pivot                      ln det (C + theta I); min_i L_ii^2 of its Cholesky factor
+ * *info (required) as LAPACK's dpotrf: 0, or k + 1 where pivot k was <= 0 or not finite (a point that is not finite);
+ * with *info != 0 the call returns 0 and writes nothing else (f and grad apart).  BIOEN_HIP_EINVAL, before the device, the
+ * point or a session are touched: theta <= 0 or not finite, nobs outside 0 .. 8, observables without nobs or the reverse,
+ * g without G.  The factor becomes the context's factor.  The same bits in give the same bits out; k observables in one
+ * call give the bits of k calls.  The device buffers are those of bioen_logwn_cov, the Newton entries,
+ * bioen_laplace_forces and bioen_hip_forces_colquad (bioen_hip_ctx_footprint: bits 10, 8, 9, 6). */
+int bioen_logwn_laplace(bioen_hip_ctx* ctx, const double* g, const double* G, double theta, const double* observables, int nobs,
+                        double* std_averages, double* cov_averages, double* w, double* leverage, double* var_logw,
+                        double* std_w, double* obs_averages, double* var_observables, double* logdet, double* min_pivot,
+                        int* info, double* f, double* grad);
+
 #ifdef __cplusplus
 }
 #endif
