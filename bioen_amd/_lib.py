@@ -203,6 +203,8 @@ _SIGNATURES = {
     "bioen_logwn_cov_bf16": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, dp, dp]),
     "bioen_logwn_series": (C.c_int, [ctx_p, dp, dp, dp, C.c_int, C.POINTER(LogwNewtonConfig), C.c_int, C.c_int, dp,
                                      C.POINTER(LogwNewtonSeriesResult)]),
+    "bioen_logwn_profile_series": (C.c_int, [ctx_p, dp, dp, dp, C.c_int, C.POINTER(LogwNewtonConfig), C.c_int, C.c_int, dp, ip,
+                                             C.c_int, dp, dp, dp, dp, C.POINTER(LogwNewtonSeriesResult)]),
     "bioen_logwn_laplace": (C.c_int, [ctx_p, dp, dp, C.c_double, dp, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, ip, dp, dp]),
 }
 
@@ -538,7 +540,8 @@ class Context(object):
         f, b = C.c_int(0), C.c_longlong(0)
         check(lib().bioen_hip_ctx_footprint(self._h, C.byref(f), C.byref(b)))
         names = {1: "rowmajor", 2: "strips", 4: "strips_colsum", 8: "reduced", 16: "bfgs_hinv", 32: "forces_gram",
-                 64: "forces_colquad", 128: "forces_gram_bf16", 256: "forces_newton", 512: "forces_laplace", 1024: "logw_gram"}
+                 64: "forces_colquad", 128: "forces_gram_bf16", 256: "forces_newton", 512: "forces_laplace", 1024: "logw_gram",
+                 2048: "logw_profile"}
         return {names[k] for k in names if f.value & k}, b.value
 
     def layout(self):
@@ -780,6 +783,45 @@ class Context(object):
         return [dict(g=out[k].copy(), status=r.status, fmin=r.fmin, gmax=r.gmax, wmax=r.wmax, iterations=r.iterations,
                      evaluations=r.evaluations, factorisations=r.factorisations, bf16_passes=r.bf16_passes,
                      switched=bool(r.switched)) for k, r in enumerate(res)]
+
+    def opt_dual_newton_logw_profile_series(self, thetas, g0, G, params=None, groups=None, row_offset=None, hessian="gram",
+                                            warm=True):
+        """opt_dual_newton_logw_series with the nuisance scales of the affine model profiled out
+        (bioen_logwn_profile_series): the resident matrix is the parameter-independent one, `groups` a list of
+        row-index arrays (None: one group of all rows; rows in no group keep the scale 1; at most 64 groups), one
+        least-squares scale per group -- nuisance.refit_scales at the point's raw averages -- formed inside every
+        evaluation, the Newton step from the projected covariance.  One run per theta replaces the alternation optimise /
+        refit.  -> a list of opt_dual_newton_logw_series's dicts plus scales (one per group), chi2 and kl.  Afterwards the
+        context's affine model is (row_offset, the last theta's scales) and the last returned point is the kept point:
+        logw_hessp, logw_cov and logw_laplace without g serve it at those fixed scales.  set_affine(None, None) removes
+        the model."""
+        p = dict(params or {})
+        source = logw_newton_source(p.get("hessian", hessian))
+        th = as_f64(np.asarray(thetas, dtype=np.float64).reshape(-1))
+        g0, G = self._nvec(g0, "g0"), self._nvec(G, "G")
+        if groups is None:
+            groups = [np.arange(self.m)]
+        group = np.full(self.m, -1, dtype=np.int32)
+        for k, ix in enumerate(groups):
+            ix = np.asarray(ix, dtype=np.int64).reshape(-1)
+            if ix.size and (ix.min() < 0 or ix.max() >= self.m):
+                raise ValueError("groups: row %d outside 0 .. %d" % (ix.min() if ix.min() < 0 else ix.max(), self.m - 1))
+            if (group[ix] >= 0).any() or np.unique(ix).size != ix.size:
+                raise ValueError("groups must be disjoint")
+            group[ix] = k
+        off = None if row_offset is None else self._mvec(row_offset, "row_offset")
+        cfg = logw_newton_config(p)
+        nt, ng = max(len(th), 1), max(len(groups), 1)
+        out, scales, chi2, kl = np.empty((nt, self.n)), np.empty((nt, ng)), np.empty(nt), np.empty(nt)
+        res = (LogwNewtonSeriesResult * nt)()
+        check(lib().bioen_logwn_profile_series(self._h, ptr(g0), ptr(G), ptr(th), int(len(th)), C.byref(cfg), source,
+                                               int(bool(warm)), ptr(off) if off is not None else None,
+                                               group.ctypes.data_as(ip), int(len(groups)), ptr(out), ptr(scales), ptr(chi2),
+                                               ptr(kl), res))
+        return [dict(g=out[k].copy(), status=r.status, fmin=r.fmin, gmax=r.gmax, wmax=r.wmax, iterations=r.iterations,
+                     evaluations=r.evaluations, factorisations=r.factorisations, bf16_passes=r.bf16_passes,
+                     switched=bool(r.switched), scales=[float(s) for s in scales[k]], chi2=float(chi2[k]), kl=float(kl[k]))
+                for k, r in enumerate(res)]
 
     def opt_lbfgs_logw(self, g0, G, theta, params, verbose=False, debug=False, want_weights=True):
         g0, G = self._nvec(g0, "g0"), self._nvec(G, "G")

@@ -27,9 +27,6 @@ static int logwn_keep_point(bioen_hip_ctx* c, double theta, double* f, const cha
     return logwn_copies(c, who);
 }
 
-// the covariance's source: the FP64 pass (k_logw_gram) or the split-BF16 one (k_logw_gram_bf16)
-enum LogwnSource : int { LOGWN_FP64 = 0, LOGWN_BF16 = 1 };
-
 // C of the kept log-weights point into SCRATCH_LOGW_GRAM, not downloaded; negb (may be NULL): -Yc grad for the solve (the
 // same bits from either source)
 int logwn_gram(bioen_hip_ctx* c, int source, const double** cov, double* negb) {
@@ -78,7 +75,7 @@ static int logwn_cov_entry(bioen_hip_ctx* c, const double* g, const double* G, d
 }
 
 // what bioen_logwn_opt and bioen_logwn_series refuse before the device, the point or a session are touched
-static int logwn_check(const bioen_logwn_config* cfg, const double* thetas, int ntheta, const char* who) {
+int logwn_check(const bioen_logwn_config* cfg, const double* thetas, int ntheta, const char* who) {
     if (!(cfg->gtol >= 0.0) || cfg->max_iterations < 0 || cfg->max_halvings < 1 || !(cfg->armijo > 0.0) || !(cfg->floor_ulps >= 0.0))
         return fail(BIOEN_HIP_EINVAL, "bioen_logwn_config: gtol >= 0, max_iterations >= 0, max_halvings >= 1, armijo > 0, floor_ulps >= 0");
     for (int k = 0; k < ntheta; ++k)
@@ -90,9 +87,10 @@ static int logwn_check(const bioen_logwn_config* cfg, const double* thetas, int 
 // The loop for one theta and one covariance source, from the point slot 0's xp holds (c->fixed = G): DESIGN 6j, and 6k's
 // switch -- with LOGWN_BF16 a step rejected at the rounding floor does not end the run: the kept point is restored and the
 // FP64 pass serves the rest of this theta (once; res->switched).  Leaves the returned point in xp, evaluated and kept; every
-// status returns 0.
-static int logwn_loop(bioen_hip_ctx* c, double theta, const bioen_logwn_config* cfg, int source,
-                      bioen_logwn_series_result* res, const char* who) {
+// status returns 0.  While the context's profile selection is set (api_logw_profile.cpp) every evaluation forms the
+// scales, and C and -b are projected behind the Gram finish: the loop is the same.
+int logwn_loop(bioen_hip_ctx* c, double theta, const bioen_logwn_config* cfg, int source, bioen_logwn_series_result* res,
+               const char* who) {
     int rc;
     const double eps = 2.220446049250313e-16;
     ProblemSlot& s0 = c->slot[0];
@@ -113,7 +111,9 @@ static int logwn_loop(bioen_hip_ctx* c, double theta, const bioen_logwn_config* 
     const int one[1] = {0};
     int status = -1, at_x = 1;
     for (;;) {
-        if (gmax <= cfg->gtol * wmax && cmax <= theta) {      // 1. the gradient test, and gamma's
+        // 1. the gradient test, and gamma's -- at a finite point: the maxima of a point that is not finite are not its own (fmax
+        // passes over a NaN), and it goes on to 3, where C + theta I does not factorise
+        if (std::isfinite(f) && gmax <= cfg->gtol * wmax && cmax <= theta) {
             status = 0;
             break;
         }
@@ -125,6 +125,7 @@ static int logwn_loop(bioen_hip_ctx* c, double theta, const bioen_logwn_config* 
         const double* cov = nullptr;
         if ((rc = logwn_gram(c, source, &cov, nb.X))) return rc;
         if (source == LOGWN_BF16) ++res->bf16_passes;
+        if (c->profile_groups > 0) launch_logw_project(c, c->point_ybar, const_cast<double*>(cov), nb.X);
         int info = 0;
         if ((rc = fnewton_factor(c, cov, theta, &info, nullptr))) return rc;
         ++res->factorisations;

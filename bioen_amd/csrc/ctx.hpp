@@ -160,6 +160,8 @@ enum CtxScratch : int {
                          // diag L, diag H^-1 and diag C H^-1 C (mp each)
     SCRATCH_LOGW_GRAM,   // the log-weights dual Newton (api_logw_newton.inl): k_logw_gram's sets, their sum, C, and the loop's scalars
                          // (kernels.hpp: logw_gram_plan)
+    SCRATCH_LOGW_PROFILE,// the dual Newton with the nuisance scales profiled out (api_logw_profile.cpp): the scales, vhat, q, T and
+                         // the rows' groups (kernels.hpp: logw_profile_layout)
     SCRATCH_COUNT
 };
 struct CtxScratchBuf {
@@ -325,6 +327,9 @@ struct bioen_hip_ctx {
     int fgram_fresh = 0;                 // 1: SCRATCH_GRAM holds C and H of the kept forces point (fgram_compute, source 0); goes with the point
     int fnewton_state = 0;               // 0: no factor yet, 1: L is complete, 2: the last factorisation ended with info != 0
     int fnewton_info = 0;                // ... that info
+    // > 0: the nuisance scales of that many row groups are profiled out -- launch_rows_combine runs the profiled
+    // combine, the dual Newton loop projects C and -b.  Set on entry of bioen_logwn_profile_series, cleared on every way out
+    int profile_groups = 0;
 
     // RCCL (lazy, dlopen)
     void* comm = nullptr;

@@ -95,6 +95,14 @@ int logwn_copies(const bioen_hip_ctx* c, const char* who);
 // C of the kept log-weights point into SCRATCH_LOGW_GRAM, not downloaded (source 0: the FP64 pass, 1: the split-BF16 one);
 // negb (may be NULL): -Yc grad
 int logwn_gram(bioen_hip_ctx* c, int source, const double** cov, double* negb);
+// the covariance's source: the FP64 pass (k_logw_gram) or the split-BF16 one (k_logw_gram_bf16)
+enum LogwnSource : int { LOGWN_FP64 = 0, LOGWN_BF16 = 1 };
+// what the dual Newton entries refuse before the device, the point or a session are touched: the config, a theta <= 0
+int logwn_check(const bioen_logwn_config* cfg, const double* thetas, int ntheta, const char* who);
+// the dual Newton loop for one theta from the point slot 0's xp holds (c->fixed = G); leaves the returned point in xp,
+// evaluated and kept; every status returns 0
+int logwn_loop(bioen_hip_ctx* c, double theta, const bioen_logwn_config* cfg, int source, bioen_logwn_series_result* res,
+               const char* who);
 
 }  // namespace bioen
 #pragma GCC visibility pop

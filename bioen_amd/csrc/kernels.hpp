@@ -227,6 +227,19 @@ void launch_logwn_stats(bioen_hip_ctx* c, const double* x, const double* e, cons
 void launch_logwn_step(bioen_hip_ctx* c, const double* x, const double* cadj, const double* grad, const double* pscal,
                        double theta, double* u, double* out);
 
+// ---- the dual Newton with the nuisance scales profiled out (kernels_logw_profile.hip) ------------------------
+struct LogwProfileBuf {                 // where the parts of SCRATCH_LOGW_PROFILE stand
+    double *scales, *vhat, *q, *T;      // s_k [64]; vhat [mp]; q [64][64]; T [64][mp + 1]
+    int* group;                         // [mp]: the group of a row, -1: none (the padding rows too)
+};
+size_t logw_profile_doubles(const bioen_hip_ctx* c);
+LogwProfileBuf logw_profile_layout(const bioen_hip_ctx* c, double* base);
+// launch_rows_combine's log-weights form for K = 1 with c->profile_groups groups: the scales from the raw averages, sigma into
+// c->row_scale, then the rows' finish (launch_rows_combine hands over to it while the selection is set)
+void launch_rows_combine_profile(bioen_hip_ctx* c, const Round& r, const double* center);
+// behind launch_logw_gram: cov (m x m) <- Pi cov Pi on the lower triangle, mirrored; negb <- Pi negb; ybar: the point's raw averages
+void launch_logw_project(bioen_hip_ctx* c, const double* ybar, double* cov, double* negb);
+
 // ---- the log-weights method's Laplace error bars at the kept point (kernels_logw_laplace.hip): what stands
 // between k_logw_gram, the factor, its inverse P = (C + theta I)^-1 and k_forces_colquad's pass ---------------------------
 // Ca (m x m, dense, bitwise symmetric) <- I - theta P; ybp [m] <- ybar - strip centre (k_forces_colquad's ybar')

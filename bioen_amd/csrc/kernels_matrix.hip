@@ -633,6 +633,10 @@ int combine_grid(const bioen_hip_ctx*) { return 1; }
 
 void launch_rows_combine(bioen_hip_ctx* c, const Round& r, bool logw, const double* center, bool store_raw,
                          const DevGate* gatep) {
+    if (logw && c->profile_groups > 0 && r.n == 1 && store_raw && !gatep) {      // the scales are formed in the combine
+        launch_rows_combine_profile(c, r, center);
+        return;
+    }
     MVec8 part;
     for (int a = 0; a < kMaxBatch; ++a) part.p[a] = a < r.n ? r.part[a] : nullptr;
     DevGate gate{};

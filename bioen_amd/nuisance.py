@@ -14,7 +14,8 @@ m- (c-) independent matrix resident in HBM, step 2 needs one GEMV (yraw = Y . w,
 closed-form 1-D least-squares solution per group of rows, and step 1 sees the new parameter through
 ``Context.set_affine`` -- nothing is rebuilt or re-uploaded.
 
-``series`` runs the loop for the log-weights method, ``series_forces`` for the forces method.
+``series`` runs the loop for the log-weights method, ``series_forces`` for the forces method.  ``series_profiled`` reaches
+the loop's fixed point without alternating: the refit is part of every evaluation of a dual Newton run.
 """
 import numpy as np
 
@@ -72,6 +73,39 @@ def series(ctx, thetas, G, g_init, lbfgs_params, YTilde, groups=None, row_offset
         out.append({"theta": float(theta), "w": w, "g": g, "fmin": info.fmin, "chi2": info.chi2, "S": -info.kl,
                     "scales": list(scales), "trace": trace})
     ctx.set_affine(None, None)
+    return out
+
+
+def series_profiled(ctx, thetas, G, g_init, params, groups=None, row_offset=None, hessian="gram", warm=True):
+    """The theta-series of ``series`` without the alternation: the scales are profiled out inside the
+    evaluation -- at every point they are ``refit_scales`` of that point's raw averages -- and the dual Newton minimizer of
+    the log-weights method (``Context.opt_dual_newton_logw_profile_series``) runs once per theta, its step from the projected
+    covariance.  The optimum is the fixed point the alternation converges to.
+
+    ctx, groups, row_offset : as in ``series`` (at most 64 groups; rows in no group keep the scale 1)
+    params   : the dual Newton's (gtol, max_iterations, ...; ``bioen_amd._lib.LOGW_NEWTON_DEFAULTS``)
+    hessian  : "gram" | "gram_bf16", the covariance of the step
+    warm     : theta k starts at the optimum of theta k - 1 (False: every theta at g_init, as ``series`` does)
+    There are no start values for the scales: they are a function of the point.  A theta that does not end with status 0
+    raises RuntimeError.  The model is removed from the context at the end, also when the call raises.
+    Returns a list of dicts per theta: theta, w, g, fmin, chi2, S, scales, status, iterations, evaluations, factorisations,
+    bf16_passes, switched."""
+    try:
+        res = ctx.opt_dual_newton_logw_profile_series(thetas, g_init, G, params, groups=groups, row_offset=row_offset,
+                                                      hessian=hessian, warm=warm)
+        out = []
+        for theta, r in zip(thetas, res):
+            if r["status"] != 0:
+                raise RuntimeError("nuisance.series_profiled, theta = %g: dual Newton return code %d after %d iterations"
+                                   % (theta, r["status"], r["iterations"]))
+            w = np.exp(r["g"] - r["g"].max())
+            w /= w.sum()
+            out.append({"theta": float(theta), "w": w, "g": r["g"], "fmin": r["fmin"], "chi2": r["chi2"], "S": -r["kl"],
+                        "scales": list(r["scales"]), "status": r["status"], "iterations": r["iterations"],
+                        "evaluations": r["evaluations"], "factorisations": r["factorisations"],
+                        "bf16_passes": r["bf16_passes"], "switched": r["switched"]})
+    finally:
+        ctx.set_affine(None, None)
     return out
 
 

@@ -352,37 +352,59 @@ def dual_newton_bioen_log_posterior_base(gInit, G, yTilde, YTilde, theta, params
 
     -> dict(g, fmin, status, iterations, evaluations, factorisations, gmax, wmax, bf16_passes, switched).  theta <= 0 is
     refused: the step divides by theta."""
-    theta = float(theta)
-    if not theta > 0.0:
-        raise RuntimeError("dual_newton needs theta > 0 (the step divides by theta), got %r" % theta)
+    theta = _dual_newton_theta(theta)
     source = _dual_newton_source(params)
     sources = dict(dict(gram=lambda p, yT, centre: dual_newton_covariance(p, yT), gram_bf16=dual_newton_covariance_bf16),
                    **(cov or {}))
-    c_ = dict(_DUAL_NEWTON_CONSTANTS, **{k: v for k, v in dict(params).items() if k in _DUAL_NEWTON_CONSTANTS})
-    gtol, maxit = float(params.get("gtol", 1e-6)), int(params.get("max_iterations", 200))
     yT = np.asarray(yTilde, dtype=np.float64)
     YT = np.asarray(YTilde, dtype=np.float64).reshape(-1)
     Gv = np.asarray(G, dtype=np.float64).reshape(-1)
-    logs0 = float(np.log(np.exp(Gv - Gv.max()).sum()) + Gv.max())
+    logs0 = _log_sum_exp(Gv)
+    return _dual_newton_loop(lambda g: _dual_newton_point(g, Gv, yT, YT, theta, logs0),
+                             lambda p, src: dual_newton_step(p, yT, theta, C=sources[src](p, yT, YT))[0],
+                             gInit, theta, params, source)[0]
+
+
+def _dual_newton_theta(theta):
+    theta = float(theta)
+    if not theta > 0.0:
+        raise RuntimeError("dual_newton needs theta > 0 (the step divides by theta), got %r" % theta)
+    return theta
+
+
+def _log_sum_exp(Gv):
+    return float(np.log(np.exp(Gv - Gv.max()).sum()) + Gv.max())
+
+
+def _dual_newton_loop(point, step, gInit, theta, params, source):
+    """The decisions 1 .. 5 of dual_newton_bioen_log_posterior_base on a point function g -> dict(g, f, w, gamma, grad, ...)
+    and a step function (p, source) -> u: what the plain and the profiled minimizer share"""
+    c_ = dict(_DUAL_NEWTON_CONSTANTS, **{k: v for k, v in dict(params).items() if k in _DUAL_NEWTON_CONSTANTS})
+    gtol, maxit = float(params.get("gtol", 1e-6)), int(params.get("max_iterations", 200))
     eps = np.finfo(np.float64).eps
-    p = _dual_newton_point(np.asarray(gInit, dtype=np.float64).reshape(-1).copy(), Gv, yT, YT, theta, logs0)
+    p = point(np.asarray(gInit, dtype=np.float64).reshape(-1).copy())
     count = dict(iterations=0, evaluations=1, factorisations=0, bf16_passes=0)
     status, switched = None, False
     while status is None:
         gmax, wmax = float(np.abs(p["grad"]).max()), float(p["w"].max())
-        if gmax <= gtol * wmax and float(np.abs(p["gamma"]).max()) <= theta:
+        if np.isfinite(p["f"]) and gmax <= gtol * wmax and float(np.abs(p["gamma"]).max()) <= theta:
             status = 0
             break
         if count["iterations"] >= maxit:
             status = 1
             break
-        u, _ = dual_newton_step(p, yT, theta, C=sources[source](p, yT, YT))
+        if not np.isfinite(p["f"]):                 # C + theta I of a point that is not finite does not factorise
+            count["factorisations"] += 1
+            count["bf16_passes"] += source == "gram_bf16"
+            status = 3
+            break
+        u = step(p, source)
         count["factorisations"] += 1
         count["bf16_passes"] += source == "gram_bf16"
         slope = float(p["grad"].dot(u))
         alpha, trial, go_over = 1.0, None, False
         for _ in range(int(c_["max_halvings"])):
-            q = _dual_newton_point(p["g"] + alpha * u, Gv, yT, YT, theta, logs0)
+            q = point(p["g"] + alpha * u)
             count["evaluations"] += 1
             floor = abs(alpha * slope) <= c_["floor_ulps"] * eps * abs(p["f"])
             if floor:
@@ -407,7 +429,7 @@ def dual_newton_bioen_log_posterior_base(gInit, G, yTilde, YTilde, theta, params
         p = trial
         count["iterations"] += 1
     return dict(count, g=p["g"], fmin=p["f"], status=status, gmax=float(np.abs(p["grad"]).max()),
-                wmax=float(p["w"].max()), switched=switched)
+                wmax=float(p["w"].max()), switched=switched), p
 
 
 def dual_newton_series_base(gInit, G, yTilde, YTilde, thetas, params, warm=True):
@@ -421,6 +443,119 @@ def dual_newton_series_base(gInit, G, yTilde, YTilde, thetas, params, warm=True)
     out = []
     for t in thetas:
         out.append(dual_newton_bioen_log_posterior_base(g, G, yTilde, YTilde, t, params))
+        if warm:
+            g = out[-1]["g"]
+    return out
+
+
+# ------------------------------------------------------------------ nuisance scales profiled out
+# The affine model r = off + sigma o (Y w) - YTilde with one least-squares scale s_k per group of rows, sigma_i = s_group(i):
+# the scales are a function of the point (nuisance.refit_scales's closed form at ybar = Y w), the profile objective
+#   phi(g) = theta KL(w || w0) + 1/2 r^T r     has the gradient of the affine objective at row_scale = sigma (envelope:
+# d/ds_k 1/2 r^T r = sum_{i in k} r_i ybar_i = 0 at s_k), and its Gauss-Newton Hessian is theta S_w + W Yc^T S Pi S Yc W,
+# Pi = I - sum_k vhat_k vhat_k^T, vhat_k = ybar restricted to group k, normalised (Kaufman's variable projection).
+def _profile_groups(groups, m):
+    """groups (None: one group of all rows) -> a list of sorted int64 index arrays, checked: disjoint, inside 0 .. m - 1,
+    none empty"""
+    if groups is None:
+        groups = [np.arange(m)]
+    out = [np.unique(np.asarray(ix, dtype=np.int64).reshape(-1)) for ix in groups]
+    seen = np.zeros(m, dtype=np.int64)
+    for ix in out:
+        if ix.size == 0 or ix.min() < 0 or ix.max() >= m:
+            raise RuntimeError("dual_newton profile: a group is empty or holds a row outside 0 .. %d" % (m - 1))
+        seen[ix] += 1
+    if not out or seen.max() > 1:
+        raise RuntimeError("dual_newton profile: the groups must be disjoint, and at least one")
+    return out
+
+
+def _dual_newton_profile_point(g, G, Y, YT, theta, logs0, groups, off):
+    """_dual_newton_point on the profiled model: the scales are formed from the raw averages between the forward pass
+    and the residual; ybar stays the RAW average Y w"""
+    shift = g.max()
+    e = np.exp(g - shift)
+    s = e.sum()
+    w = e / s
+    ybar = Y.dot(w)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        scales = np.array([ybar[ix].dot(YT[ix] - off[ix]) / ybar[ix].dot(ybar[ix]) for ix in groups])
+    sigma = np.ones(Y.shape[0])
+    for sk, ix in zip(scales, groups):
+        sigma[ix] = sk
+    r = off + sigma * ybar - YT
+    sr = sigma * r
+    dev = g - G
+    P = float(w.dot(dev))
+    f = float(theta * (P - (np.log(s) + shift) + logs0) + 0.5 * r.dot(r))
+    gamma = theta * (dev - P) + (Y.T.dot(sr) - float(ybar.dot(sr)))
+    return dict(g=g, f=f, w=w, ybar=ybar, r=r, dev=dev, P=P, gamma=gamma, grad=w * gamma, scales=scales, sigma=sigma)
+
+
+def dual_newton_profile_covariance(p, Y, groups, C=None):
+    """(C_Pi, b_Pi, V) at a point of _dual_newton_profile_point: C_A = S C S and b_A = S Yc grad projected by
+    Pi = I - V V^T, V's columns the vhat_k.  C: the raw covariance from another source than dual_newton_covariance.
+    C_Pi is formed on the lower triangle from T = V^T C_A and q = T V and mirrored: symmetric bit for bit."""
+    Yc = Y - p["ybar"][:, None]
+    if C is None:
+        C = (Yc * p["w"]).dot(Yc.T)
+    sg = p["sigma"]
+    CA = (sg[:, None] * C) * sg[None, :]
+    b = sg * Yc.dot(p["grad"])
+    m = Y.shape[0]
+    V = np.zeros((m, len(groups)))
+    for k, ix in enumerate(groups):
+        V[ix, k] = p["ybar"][ix] / np.sqrt(p["ybar"][ix].dot(p["ybar"][ix]))
+    T = V.T.dot(CA)
+    q = T.dot(V)
+    CP = CA - V.dot(T) - T.T.dot(V.T) + V.dot(q).dot(V.T)
+    CP = np.tril(CP) + np.tril(CP, -1).T
+    return CP, b - V.dot(V.T.dot(b)), V
+
+
+def dual_newton_profile_step(p, Y, theta, groups, C=None):
+    """(u, z) of the profiled minimizer: (C_Pi + theta I) z = -b_Pi (SPD for every theta > 0; z in the range of Pi),
+    u = -[(dev - P) + (1 / theta) Yc^T (sigma o (r + z))]"""
+    import scipy.linalg
+    CP, bP, _ = dual_newton_profile_covariance(p, Y, groups, C)
+    L = np.linalg.cholesky(CP + theta * np.eye(CP.shape[0]))
+    z = -scipy.linalg.cho_solve((L, True), bP)
+    Yc = Y - p["ybar"][:, None]
+    u = -((p["dev"] - p["P"]) + Yc.T.dot(p["sigma"] * (p["r"] + z)) / theta)
+    return u, z
+
+
+def dual_newton_profile_base(gInit, G, Y, YTilde, theta, params, groups, row_offset=None):
+    """The numpy statement of the dual Newton minimizer with the nuisance scales profiled out, the
+    specification of bioen_logwn_profile_series's loop: dual_newton_bioen_log_posterior_base decision for decision, on
+    _dual_newton_profile_point and dual_newton_profile_step.  Y: the parameter-independent matrix; groups: a list of row
+    index arrays (None: one group of all rows), rows in no group keep the scale 1.  -> its dict plus scales (one per
+    group, at the returned point)."""
+    theta = _dual_newton_theta(theta)
+    source = _dual_newton_source(params)
+    Ym = np.asarray(Y, dtype=np.float64)
+    YT = np.asarray(YTilde, dtype=np.float64).reshape(-1)
+    off = np.zeros_like(YT) if row_offset is None else np.asarray(row_offset, dtype=np.float64).reshape(-1)
+    Gv = np.asarray(G, dtype=np.float64).reshape(-1)
+    gr = _profile_groups(groups, Ym.shape[0])
+    logs0 = _log_sum_exp(Gv)
+    raw = dict(gram=lambda p: None, gram_bf16=lambda p: dual_newton_covariance_bf16(p, Ym, YT))
+    res, p = _dual_newton_loop(lambda g: _dual_newton_profile_point(g, Gv, Ym, YT, theta, logs0, gr, off),
+                               lambda p, src: dual_newton_profile_step(p, Ym, theta, gr, C=raw[src](p))[0],
+                               gInit, theta, params, source)
+    return dict(res, scales=[float(s) for s in p["scales"]])
+
+
+def dual_newton_profile_series_base(gInit, G, Y, YTilde, thetas, params, groups, row_offset=None, warm=True):
+    """dual_newton_series_base for the profiled minimizer: the numpy statement of
+    Context.opt_dual_newton_logw_profile_series"""
+    thetas = [float(t) for t in thetas]
+    if not thetas or not all(t > 0.0 and np.isfinite(t) for t in thetas):
+        raise RuntimeError("dual_newton needs at least one theta, every theta > 0 and finite, got %r" % (thetas,))
+    g = np.asarray(gInit, dtype=np.float64).reshape(-1)
+    out = []
+    for t in thetas:
+        out.append(dual_newton_profile_base(g, G, Y, YTilde, t, params, groups, row_offset))
         if warm:
             g = out[-1]["g"]
     return out

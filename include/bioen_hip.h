@@ -811,6 +811,32 @@ int bioen_logwn_laplace(bioen_hip_ctx* ctx, const double* g, const double* G, do
                         double* std_w, double* obs_averages, double* var_observables, double* logdet, double* min_pivot,
                         int* info, double* f, double* grad);
 
+/* ---- log-weights method: the dual Newton theta series with nuisance scales profiled out (DEER modulation depths, the
+ * scattering scale factor).  DESIGN section 6m.  The model is the affine one, off_i + sigma_i (Y w)_i, with ONE scale per
+ * group of rows, sigma_i = s_group[i] (group -1: the row's scale stays 1), and the scales are a function of the point:
+ *   s_k = sum_{i in k} ybar_i (YTilde_i - off_i) / sum_{i in k} ybar_i^2,  ybar = Y w the raw averages,
+ * the least-squares refit of bioen_amd.nuisance.refit_scales, formed inside every evaluation.  The minimizer is
+ * bioen_logwn_series's loop on the profile objective theta KL + 1/2 |off + sigma o ybar - YTilde|^2: its gradient is the
+ * affine model's at row_scale = sigma, its step solves (Pi C_A Pi + theta I) z = -Pi b_A with Pi the projector that removes
+ * the groups' normalised ybar.  One run replaces the alternation optimise / refit of the reference's protocol. ---- */
+
+/* source, warm, config, gopt [ntheta][n], results [ntheta], the statuses and the refusals (BIOEN_HIP_ESTATE) are
+ * bioen_logwn_series's.  row_offset [m] (NULL: zeros), group [m] with values in -1 .. ngroups - 1, 1 <= ngroups <= 64, every
+ * group with at least one row.  scales [ntheta][ngroups] (required): the scales at each theta's returned point; chi2,
+ * kl [ntheta] (either may be NULL): 1/2 sum r^2 (bioen_opt_result's chi2) and KL(w || w0) there.  There are no start values for the scales.  A group
+ * whose sum ybar^2 is 0 or not finite makes f not finite: such a trial is rejected, at the start point the run ends with
+ * status 3.  BIOEN_HIP_EINVAL, before the device, the point, the model or a session are touched: NULL arguments, ntheta <
+ * 1, any theta <= 0 or not finite, ngroups outside 1 .. 64, a group id outside -1 .. ngroups - 1, an empty group, source or
+ * warm out of range, a config bioen_logwn_opt refuses.  Returns 0 with every status; then the context's affine model
+ * (bioen_hip_ctx_set_affine's) is (row_offset, sigma of the last theta's returned point), and that point is the kept
+ * log-weights point: bioen_hip_logw_hessp, bioen_logwn_cov and bioen_logwn_laplace without g serve it at those FIXED
+ * scales.  Ends a BFGS session.  The device buffer of the scales and the projection is this section's own, allocated at
+ * the first call and freed with the context (bioen_hip_ctx_footprint: bit 11, value 2048). */
+int bioen_logwn_profile_series(bioen_hip_ctx* ctx, const double* g0, const double* G, const double* thetas, int ntheta,
+                               const bioen_logwn_config* config, int source, int warm, const double* row_offset,
+                               const int* group, int ngroups, double* gopt, double* scales, double* chi2, double* kl,
+                               bioen_logwn_series_result* results);
+
 #ifdef __cplusplus
 }
 #endif
