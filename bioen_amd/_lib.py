@@ -122,6 +122,7 @@ _SIGNATURES = {
     "bioen_hip_ctx_set_affine": (C.c_int, [ctx_p, dp, dp]),
     "bioen_hip_ctx_set_direction_mode": (C.c_int, [ctx_p, C.c_int]),
     "bioen_hip_ctx_set_storage": (C.c_int, [ctx_p, C.c_int]),
+    "bioen_hip_ctx_set_dense_panels": (C.c_int, [ctx_p, C.c_int]),
     "bioen_hip_ctx_set_one_copy": (C.c_int, [ctx_p, C.c_int]),
     "bioen_hip_synchronize": (C.c_int, [ctx_p]),
     "bioen_hip_logw_weights": (C.c_int, [ctx_p, dp, dp, dp]),
@@ -608,6 +609,19 @@ class Context(object):
         takes this form by itself when the second copy does not fit.)"""
         check(lib().bioen_hip_ctx_set_one_copy(self._h, int(bool(on))))
 
+    dense_panels = False        # what set_dense_panels left (the default of a context: off)
+
+    def set_dense_panels(self, on=True):
+        """The log-weights dual Newton beyond 1024 observables (bioen_hip_ctx_set_dense_panels): with it logw_cov,
+        logw_cov_bf16, opt_dual_newton_logw and opt_dual_newton_logw_series serve 1024 < M <= 4096 over the row panels of the
+        matrix (their strip copies must be resident); beyond 4096 rows they raise BioenHipError (invalid state) naming 4096.
+        Off by default; logw_laplace, the profiled series, every forces dense entry, sharded contexts and the
+        reduced-storage copies refuse M > 1024 as before.  Keeps the point and a session.  The Gram buffer grows with M^2:
+        (sets + 1) x 68 MB at 4096 rows (sets: 8 unless BIOEN_HIP_SEGMENTS says otherwise) plus C, the factor's 2 M^2
+        doubles (footprint(): "logw_gram", "forces_newton").  `dense_panels` holds what was set."""
+        check(lib().bioen_hip_ctx_set_dense_panels(self._h, int(bool(on))))
+        self.dense_panels = bool(on)
+
     def synchronize(self):
         check(lib().bioen_hip_synchronize(self._h))
 
@@ -670,7 +684,8 @@ class Context(object):
     def logw_cov(self, g=None, G=None, theta=None, cov=True):
         """C = sum_j w_j (y_j - ybar)(y_j - ybar)^T, w = softmax(g): the covariance of the observables (of the affine model if
         one is set) under the weights of a log-weights point, (m, m), bitwise symmetric, the same bits call after call --
-        one compute-bound pass on the FP64 matrix cores (M <= 1024).  With `g` (and G, theta) the point is
+        one compute-bound pass on the FP64 matrix cores (M <= 1024; after set_dense_panels M <= 4096 over the row panels, with
+        a buffer of (sets + 1) x (M / 64)(M / 64 + 1) / 2 x 32 KiB: 0.6 GB at 4096 rows).  With `g` (and G, theta) the point is
         evaluated first, as by logw_hessp -- f and grad are its bits --, and kept on the context: -> (C, f, grad); cov=False
         then only sets the point (C is None).  Without, at the kept log-weights point (this call's, logw_hessp's or
         opt_dual_newton_logw's): -> C; BioenHipError (invalid state) as logw_hessp raises it.  The first computing call

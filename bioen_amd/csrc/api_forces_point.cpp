@@ -80,12 +80,16 @@ const DenseReasons kLogwnReasons = {
 
 // strip_blocks: the strip passes whose copy the entry reads -- the forces method's, or fwd_strip_blocks for the log-weights
 // entries
-int dense_guard(const bioen_hip_ctx* c, const char* who, const DenseReasons& why, int (*strip_blocks)(const bioen_hip_ctx*)) {
+int dense_guard(const bioen_hip_ctx* c, const char* who, const DenseReasons& why, int (*strip_blocks)(const bioen_hip_ctx*),
+                bool over_panels) {
     const std::string w(who);
     if (c->world != 1)
         return fail(BIOEN_HIP_ESTATE, (w + " is not served on a structure-sharded context (" + why.sharded).c_str());
-    if (c->m > 1024)
+    if (c->m > 1024 && !(over_panels && c->dense_panels))
         return fail(BIOEN_HIP_ESTATE, (w + " serves M <= 1024 only (beyond, the matrix is held as row panels" + why.panels).c_str());
+    if (c->m > kDensePanelRows)
+        return fail(BIOEN_HIP_ESTATE, (w + " serves M <= 4096 over row panels (bioen_hip_ctx_set_dense_panels): use the L-BFGS "
+                                           "beyond").c_str());
     if (c->storage)
         return fail(BIOEN_HIP_ESTATE, (w + " is not served on the reduced-storage experiment's copies "
                                            "(bioen_hip_ctx_set_storage(0))").c_str());

@@ -16,15 +16,17 @@ const PointWords kLogwnPoint = {"call with g", "set a log-weights point first (b
 
 // After a point's evaluation the guard once more (dense_guard, on the copy the log-weights forward pass reads): the strip
 // copies exist by now, or never will
-int logwn_copies(const bioen_hip_ctx* c, const char* who) {
-    if (int rc = dense_guard(c, who, kLogwnReasons, fwd_strip_blocks)) return rc;
-    return c->Ys[0] ? 0 : fail(BIOEN_HIP_ESTATE, (std::string(who) + " needs the strip copies of the matrix").c_str());
+int logwn_copies(const bioen_hip_ctx* c, const char* who, bool over_panels) {
+    if (int rc = dense_guard(c, who, kLogwnReasons, fwd_strip_blocks, over_panels)) return rc;
+    for (int p = 0; p * 1024 < c->m; ++p)                   // every row panel's (M <= 1024: the one)
+        if (!c->Ys[p]) return fail(BIOEN_HIP_ESTATE, (std::string(who) + " needs the strip copies of the matrix").c_str());
+    return 0;
 }
 
 // the loop's evaluations: what slot 0's x holds becomes the kept point (k = 1: hp_vec[0] takes the adjoint of r + z)
 static int logwn_keep_point(bioen_hip_ctx* c, double theta, double* f, const char* who) {
     if (int rc = logw_keep_point(c, theta, 1, f, nullptr)) return rc;
-    return logwn_copies(c, who);
+    return logwn_copies(c, who, true);
 }
 
 // C of the kept log-weights point into SCRATCH_LOGW_GRAM, not downloaded; negb (may be NULL): -Yc grad for the solve (the
@@ -63,9 +65,9 @@ static int logwn_cov_entry(bioen_hip_ctx* c, const double* g, const double* G, d
     if (g && !G) return fail(BIOEN_HIP_EINVAL, "g without G");
     if (!g && !C) return fail(BIOEN_HIP_EINVAL, "nothing to do: no g and no C");
     int rc;
-    if ((rc = dense_guard(c, who, kLogwnReasons, fwd_strip_blocks))) return rc;
+    if ((rc = dense_guard(c, who, kLogwnReasons, fwd_strip_blocks, true))) return rc;
     if ((rc = logw_point_prologue(c, g, G, theta, 1, f, grad, who, &kLogwnPoint))) return rc;
-    if (g && (rc = logwn_copies(c, who))) return rc;
+    if (g && (rc = logwn_copies(c, who, true))) return rc;
     if (!C) return 0;
     const double* dcov = nullptr;
     if ((rc = logwn_gram(c, source, &dcov, nullptr))) return rc;
@@ -228,7 +230,7 @@ extern "C" int bioen_logwn_opt(bioen_hip_ctx* c, const double* g0, const double*
     if (!g0 || !G || !cfg || !gopt || !res) return fail(BIOEN_HIP_EINVAL, "NULL argument");
     int rc;
     if ((rc = logwn_check(cfg, &theta, 1, __func__))) return rc;
-    if ((rc = dense_guard(c, __func__, kLogwnReasons, fwd_strip_blocks))) return rc;
+    if ((rc = dense_guard(c, __func__, kLogwnReasons, fwd_strip_blocks, true))) return rc;
     if ((rc = enter(c, FX_EVALUATES, __func__))) return rc;
     *res = bioen_logwn_result{};
     if ((rc = upload_n(c, c->slot[0].xp, g0))) return rc;
@@ -257,7 +259,7 @@ extern "C" int bioen_logwn_series(bioen_hip_ctx* c, const double* g0, const doub
     if (warm != 0 && warm != 1) return fail(BIOEN_HIP_EINVAL, "bioen_logwn_series: warm is 0 or 1");
     int rc;
     if ((rc = logwn_check(cfg, thetas, ntheta, __func__))) return rc;
-    if ((rc = dense_guard(c, __func__, kLogwnReasons, fwd_strip_blocks))) return rc;
+    if ((rc = dense_guard(c, __func__, kLogwnReasons, fwd_strip_blocks, true))) return rc;
     if ((rc = enter(c, FX_EVALUATES, __func__))) return rc;
     ProblemSlot& s0 = c->slot[0];
     if ((rc = upload_n(c, s0.xp, g0))) return rc;

@@ -330,6 +330,9 @@ struct bioen_hip_ctx {
     // > 0: the nuisance scales of that many row groups are profiled out -- launch_rows_combine runs the profiled
     // combine, the dual Newton loop projects C and -b.  Set on entry of bioen_logwn_profile_series, cleared on every way out
     int profile_groups = 0;
+    // bioen_hip_ctx_set_dense_panels: the log-weights covariance and dual Newton entries serve 1024 < m <= 4096 over the
+    // row panels; off by default
+    int dense_panels = 0;
 
     // RCCL (lazy, dlopen)
     void* comm = nullptr;

@@ -44,9 +44,11 @@ struct DenseReasons {
 extern const DenseReasons kGramReasons, kColquadReasons, kNewtonReasons, kLogwnReasons;
 
 // M <= 1024, one GPU, the FP64 strip copies.  strip_blocks: the strip passes whose copy the entry reads -- the forces
-// method's, or fwd_strip_blocks for the log-weights entries
+// method's, or fwd_strip_blocks for the log-weights entries.  over_panels: the entry has a pass over row panels (DESIGN 6n:
+// the log-weights covariance and dual Newton entries) -- on a context with bioen_hip_ctx_set_dense_panels it serves
+// M <= kDensePanelRows
 int dense_guard(const bioen_hip_ctx* c, const char* who, const DenseReasons& why,
-                int (*strip_blocks)(const bioen_hip_ctx*) = forces_fused_blocks);
+                int (*strip_blocks)(const bioen_hip_ctx*) = forces_fused_blocks, bool over_panels = false);
 
 // A scratch buffer of the context (ctx.hpp: CtxScratch): allocated, zeroed, at its first use, kept until the context goes
 int ensure_scratch(bioen_hip_ctx* c, int which, size_t doubles);
@@ -91,7 +93,8 @@ void flaplace_logdet(const double* ldiag, int m, double* logdet, double* min_piv
 // ---- the covariance of the kept log-weights point (api_logw_newton.cpp) -----------------------------------------------------
 extern const PointWords kLogwnPoint;      // the refusal without a log-weights point, as the bioen_logwn_* entries word it
 // after a point's evaluation the guard once more (the strip copies exist by now, or never will)
-int logwn_copies(const bioen_hip_ctx* c, const char* who);
+// (over_panels: dense_guard's)
+int logwn_copies(const bioen_hip_ctx* c, const char* who, bool over_panels = false);
 // C of the kept log-weights point into SCRATCH_LOGW_GRAM, not downloaded (source 0: the FP64 pass, 1: the split-BF16 one);
 // negb (may be NULL): -Yc grad
 int logwn_gram(bioen_hip_ctx* c, int source, const double** cov, double* negb);

@@ -5,7 +5,9 @@
 // (fgram16_pass: k_forces_gram_bf16 and k_logw_gram_bf16), each instance with a POINT that says how many matrices a wave
 // accumulates and how a column's weights come from what the point keeps.  The two methods' points are here as well, each
 // once for both precisions: the FP64 pass forms the weights of four columns per lane, the BF16 pass those of one, handed
-// round by shuffles.
+// round by shuffles.  A pass is compiled for one of two argument structs: FGramArgs, one copy with one row count (M <= 1024),
+// or FGramPanelArgs, the row panels' copies (1024 < M <= 4096) -- the two differ only in where a wave's two
+// slices come from, and the four kernels of the first form do not see the second.
 #pragma once
 
 #include "strip.hpp"
@@ -66,6 +68,27 @@ inline FGramArgs fgram_args(const bioen_hip_ctx* c, const GramPlan& p, double* b
 }
 inline int fgram_blocks(const GramPlan& p) { return 8 * p.ntiles * ((p.nsets + 7) / 8); }
 
+// The same pass over row panels (strip.hpp: kPanelRows = 1024 rows each, the last one shorter): every panel has a strip copy
+// and a row count of its own.  In every panel but the last a 64-row slice s of the matrix is local slice s & 15 of panel
+// s >> 4, and a 128-row tile never straddles two panels; slices, sub-tiles, centres and row sums are numbered by GLOBAL row,
+// so everything behind the sets reads them as it reads FGramArgs's.  (FGramArgs's Ys and mps are panel 0's here.)
+static_assert(kDensePanelRows == kDensePanels * kPanelRows, "the dense entries' limit is whole panels");
+struct FGramPanelArgs : FGramArgs {
+    const double* Yp[kDensePanels];     // panel p's row-sum order strip copy
+    int pmps[kDensePanels];             // its strip rows
+};
+inline FGramPanelArgs fgram_panel_args(const bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* x,
+                                       const double* pscal, const double* qv) {
+    FGramPanelArgs q{};
+    static_cast<FGramArgs&>(q) = fgram_args(c, p, buf, x, pscal, qv);
+    for (int k = 0; k < kDensePanels; ++k) {
+        const bool there = k < panel_count(c);
+        q.Yp[k] = there ? c->Ys[k] : c->Ys[0];
+        q.pmps[k] = there ? panel_mps(c, k) : panel_mps(c, 0);
+    }
+    return q;
+}
+
 // A wave's share: the set (segment v, group g: tg strips), the 64-row slices si >= sj whose sub-tile it accumulates, and
 // where the lane's halves of their chunks lie in a strip.
 struct FGramWave {
@@ -73,6 +96,8 @@ struct FGramWave {
     int si, sj, ra, rb;                             // slices, their first rows
     int offa[kWaveRows / 8], offb[kWaveRows / 8];
     size_t wa, wb;
+    const double *pa, *pb;                          // FGramPanelArgs: the copies of the slices' panels, a strip's doubles
+    size_t sta, stb;                                //   there (wave-uniform: scalar registers)
 };
 
 // Blocks b and b + 8 share an XCD and its L2: the tiles of one set are numbered so that they land on one XCD, next to each
@@ -92,6 +117,31 @@ __device__ __forceinline__ bool fgram_decode(const FGramArgs& q, int lane, int w
     strip_chunk_offsets(q.mps, w.ra, w.offa);
     strip_chunk_offsets(q.mps, w.rb, w.offb);
     w.wa = (size_t)w.ra * kStripCols + (size_t)lane * 2, w.wb = (size_t)w.rb * kStripCols + (size_t)lane * 2;
+    return true;
+}
+
+// Over panels: the same sets, tiles and slices (counted over all panels: q.nsl); ra, rb stay GLOBAL rows (the centres, the
+// row sums), the chunks' places are those of the slice's rows inside its own panel's strips
+__device__ __forceinline__ bool fgram_decode(const FGramPanelArgs& q, int lane, int wave, FGramWave& w) {
+    const int xcd = blockIdx.x & 7, k = blockIdx.x >> 3;
+    w.set = (k / q.ntiles) * 8 + xcd;
+    if (w.set >= q.nsets) return false;
+    int ti, tj;
+    tile_pair(k % q.ntiles, ti, tj);
+    w.si = 2 * ti + (wave >> 1), w.sj = 2 * tj + (wave & 1);
+    if (w.si >= q.nsl || w.sj > w.si) return false;
+    w.v = w.set / q.gs, w.g = w.set - w.v * q.gs;
+    w.tg = (q.sps - w.g + q.gs - 1) / q.gs;
+    w.ra = w.si * kWaveRows, w.rb = w.sj * kWaveRows;
+    constexpr int kSlices = kPanelRows / kWaveRows;             // 16 slices a panel
+    const int pa = __builtin_amdgcn_readfirstlane(w.si / kSlices), pb = __builtin_amdgcn_readfirstlane(w.sj / kSlices);
+    const int la = (w.si % kSlices) * kWaveRows, lb = (w.sj % kSlices) * kWaveRows;       // the slices' first rows in their panels
+    const int ma = q.pmps[pa], mb = q.pmps[pb];
+    w.pa = q.Yp[pa], w.pb = q.Yp[pb];
+    w.sta = (size_t)ma * kStripCols, w.stb = (size_t)mb * kStripCols;
+    strip_chunk_offsets(ma, la, w.offa);
+    strip_chunk_offsets(mb, lb, w.offb);
+    w.wa = (size_t)la * kStripCols + (size_t)lane * 2, w.wb = (size_t)lb * kStripCols + (size_t)lane * 2;
     return true;
 }
 
@@ -117,15 +167,34 @@ __device__ __forceinline__ void fgram_fetch(const FGramArgs& q, const FGramWave&
 #pragma unroll
     for (int c = 0; c < kWaveRows / 8; ++c) b[c] = ldg2<false>(src + w.wb + w.offb[c]);
 }
+// over panels: each slice from its own panel's copy, at that panel's stride
+__device__ __forceinline__ void fgram_fetch(const FGramPanelArgs& q, const FGramWave& w, int s, d2 (&a)[kWaveRows / 8],
+                                            d2 (&b)[kWaveRows / 8]) {
+    const size_t ph = (size_t)strip_phys(s, q.sps, q.ilv);
+    const double *sa = w.pa + ph * w.sta, *sb = w.pb + ph * w.stb;
+#pragma unroll
+    for (int c = 0; c < kWaveRows / 8; ++c) a[c] = ldg2<false>(sa + w.wa + w.offa[c]);
+#pragma unroll
+    for (int c = 0; c < kWaveRows / 8; ++c) b[c] = ldg2<false>(sb + w.wb + w.offb[c]);
+}
+
+// the first row beyond the strip rows that hold slice si: rows from there on leave no row sum
+__device__ __forceinline__ int fgram_row_limit(const FGramArgs& q, const FGramWave&) { return q.mps; }
+__device__ __forceinline__ int fgram_row_limit(const FGramPanelArgs& q, const FGramWave& w) {
+    const int p = w.ra / kPanelRows;
+    return p * kPanelRows + q.pmps[p];
+}
 
 // rs: the lane's share of the row sums of Y' u2 (slice si).  One writer per slice and set: the waves of sub-tile column 0.
-__device__ __forceinline__ void fgram_store_row_sums(const FGramArgs& q, const FGramWave& w, int lq, int lr, const double (&rs)[4]) {
+// limit: fgram_row_limit's
+__device__ __forceinline__ void fgram_store_row_sums(const FGramArgs& q, const FGramWave& w, int lq, int lr, const double (&rs)[4],
+                                                     int limit) {
     if (w.sj != 0) return;                          // (wave-uniform)
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
         const double t = quad_sum(rs[h]);
         const int row = w.ra + 16 * h + lr;
-        if (lq == 0) q.partial[(size_t)w.set * q.set_stride + q.rows_at + row] = row < q.mps ? t : 0.0;
+        if (lq == 0) q.partial[(size_t)w.set * q.set_stride + q.rows_at + row] = row < limit ? t : 0.0;
     }
 }
 
@@ -218,8 +287,9 @@ __device__ __forceinline__ fl4 mfma16(u2v a, u2v b, fl4 c) {
 // with no transpose and no LDS image.  A wave owns a 64 x 64 sub-tile of Point::kMats matrices (16 accumulators of 4 doubles
 // each), matrix 0 weighted by u1, matrix 1 by u2; the row sums of Y' u2 ride along, and with Point::kSumU2 sum u2 itself.
 // Point: a four-column point, the strip's columns 4 qq + (lane >> 4), qq = 0 .. 3.
-template <class Point>
-__device__ __forceinline__ void fgram_pass(const FGramArgs& q) {
+// Args: FGramArgs, or FGramPanelArgs -- decode, fetch and the row sums' limit are chosen by it, nothing else differs.
+template <class Point, class Args>
+__device__ __forceinline__ void fgram_pass(const Args& q) {
     constexpr int kMats = Point::kMats;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -305,7 +375,7 @@ __device__ __forceinline__ void fgram_pass(const FGramArgs& q) {
             for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int mat = 0; mat < kMats; ++mat) dst[((mat * 16 + h * 4 + gb) * 4 + r) * 64] = acc[mat][h][gb][r];
-    fgram_store_row_sums(q, w, lq, lr, rs);
+    fgram_store_row_sums(q, w, lq, lr, rs, fgram_row_limit(q, w));
     if constexpr (Point::kSumU2)
         if (w.si == 0) {                            // (sj = 0 too) over the set's columns: the four quarters hold four columns each
             const double t = quad_sum(sg);
@@ -328,8 +398,8 @@ __device__ __forceinline__ void fgram_pass(const FGramArgs& q) {
 // finishing kernels take them as they are.
 // Point: a one-column point, the strip's column lane & 15 -- a lane forms the weights of ONE column with the operations of
 // the four-column point (the same bits), the lanes that multiply with them receive them by shuffles.
-template <class Point>
-__device__ __forceinline__ void fgram16_pass(const FGramArgs& q) {
+template <class Point, class Args>
+__device__ __forceinline__ void fgram16_pass(const Args& q) {
     constexpr int kMats = Point::kMats;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -425,7 +495,7 @@ __device__ __forceinline__ void fgram16_pass(const FGramArgs& q) {
 #pragma unroll
                 for (int mat = 0; mat < kMats; ++mat)
                     dst[((mat * 16 + h * 4 + gb) * 4 + lq) * 64 + 16 * r] = (double)acc[mat][h][gb][r];
-    fgram_store_row_sums(q, w, lq, lr, rs);
+    fgram_store_row_sums(q, w, lq, lr, rs, fgram_row_limit(q, w));
     if constexpr (Point::kSumU2)
         if (w.si == 0) {                            // (sj = 0 too) as fgram_pass leaves it
             const double t = quad_sum(sg);

@@ -214,6 +214,8 @@ void launch_fgram_sum_sets(bioen_hip_ctx* c, double* buf, size_t set_stride, int
 // vector kernels of the loop around it --------------------------------------------------------------------------------
 enum LogwnScal : int { LN_GMAX = 0, LN_WMAX, LN_GAMMA, LN_SLOPE, kLogwnScal = 8 };
 GramPlan logw_gram_plan(const bioen_hip_ctx* c);
+// what the pass serves over row panels (k_logw_gram_panels, k_logw_gram_bf16_panels): four panels of 1024 rows
+constexpr int kDensePanels = 4, kDensePanelRows = 4096;
 // the sets, their sum, C (affine model: S C S) at buf + cov_at; negb (may be NULL, mp doubles) <- -Yc grad (affine: S .);
 // bf16: the sets from k_logw_gram_bf16 (split-BF16 products; -b keeps k_logw_gram's bits), everything behind them unchanged
 void launch_logw_gram(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* e, const double* grad,
@@ -263,6 +265,8 @@ constexpr int kFNewtonPanel = 64;           // columns of a panel: a diagonal ti
 void launch_fnewton_factor(bioen_hip_ctx* c, const double* src, int lds, double lambda, double* L, int ldl, double* dg, int* info);
 // X [k][ldx] <- (L L^T)^-1 X, k <= kMaxBatch
 void launch_fnewton_solve(bioen_hip_ctx* c, const double* L, int ldl, int k, double* X, int ldx);
+// the same for m > 1024 (kernels_forces_newton_wide.hip): launch_fnewton_solve hands over to it
+void launch_fnewton_solve_wide(bioen_hip_ctx* c, const double* L, int ldl, int k, double* X, int ldx);
 
 // ---- from the resident factor to the Laplace error bars, M <= 1024 (kernels_forces_laplace.hip) ---------------
 // W (ldw x ldw) <- L^-1, Hi (m x m, dense, bitwise symmetric) <- W^T W, ldiag <- diag L

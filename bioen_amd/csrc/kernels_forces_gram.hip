@@ -92,8 +92,8 @@ __global__ __launch_bounds__(256) void k_fgram_square(const double* __restrict__
 // (segcols, M) alone
 GramPlan gram_plan(const bioen_hip_ctx* c, int mats, int set_extra, size_t tail) {
     GramPlan p{};
-    const int mps = panel_mps(c, 0);
-    p.nsl = (mps + kWaveRows - 1) / kWaveRows;
+    const int np = panel_count(c);                  // over row panels (the log-weights pass): 16 slices a full panel
+    p.nsl = (np - 1) * (kPanelRows / kWaveRows) + (panel_mps(c, np - 1) + kWaveRows - 1) / kWaveRows;
     const int t = (p.nsl + 1) / 2;
     p.ntiles = t * (t + 1) / 2;
     p.nsub = p.nsl * (p.nsl + 1) / 2;

@@ -17,17 +17,11 @@
 // k_fnewton_solve: one block, L y = b then L^T x = y for k <= 8 right-hand sides; a diagonal tile is solved by one wave
 // per right-hand side (lane t owns unknown t, L11 in LDS), the rest are GEMV updates: forward a wave per 32 rows with a
 // butterfly sum (coalesced row segments), backward one column per thread.  A right-hand side's arithmetic does not depend on k: a column of a batch is the single solve.
-#include "tile64.hpp"
+// (One column per thread ends at column 1023: beyond m = 1024 launch_fnewton_solve hands over to k_fnewton_solve_wide,
+// kernels_forces_newton_wide.hip.  fnewton_lane and fnewton_solve_tile, which both use: fnewton.hpp.)
+#include "fnewton.hpp"
 
 namespace bioen {
-
-// lane `src`'s value in every lane, src wave-uniform: two scalar lane reads, no trip through LDS as __shfl takes (the
-// substitutions below are chains of these)
-__device__ __forceinline__ double fnewton_lane(double v, int src) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-    return __hiloint2double(hi, lo);
-}
 
 // L <- the lower triangle of src (m x m, row-major, leading dimension lds) + lambda I, zeros above the diagonal; dg <-
 // the diagonal of src (without lambda); *info <- 0.  Reads nothing above the diagonal.
@@ -153,20 +147,6 @@ __global__ __launch_bounds__(256) void k_fnewton_syrk(double* __restrict__ L, in
         }
 }
 
-// The solve's diagonal tile at j0 (nb rows) into t11, the identity beyond nb, and dinv <- 1 / its diagonal: one division
-// per unknown, outside the chain.  1024 threads, four loads each; ends with a barrier.
-__device__ __forceinline__ void fnewton_solve_tile(double (*t11)[kT64 + 1], double* dinv, const double* L, int ldl, int j0, int nb) {
-#pragma unroll
-    for (int it = 0; it < kT64 * kT64 / 1024; ++it) {
-        const int e = threadIdx.x + 1024 * it;
-        const int r = e / kT64, s = e % kT64;
-        const double v = (r < nb && s <= r) ? L[(size_t)(j0 + r) * ldl + j0 + s] : (r == s ? 1.0 : 0.0);
-        t11[r][s] = v;
-        if (r == s) dinv[r] = 1.0 / v;
-    }
-    __syncthreads();
-}
-
 // X: [k][ldx], right-hand sides in, solutions out.  1024 threads; wave a < k solves the diagonal tiles of right-hand side a.
 __global__ __launch_bounds__(1024) void k_fnewton_solve(const double* __restrict__ L, int ldl, int m, int k, double* __restrict__ X,
                                                         int ldx) {
@@ -272,6 +252,7 @@ void launch_fnewton_factor(bioen_hip_ctx* c, const double* src, int lds, double 
 
 // X [k][ldx] <- (L L^T)^-1 X
 void launch_fnewton_solve(bioen_hip_ctx* c, const double* L, int ldl, int k, double* X, int ldx) {
+    if (c->m > 1024) return launch_fnewton_solve_wide(c, L, ldl, k, X, ldx);
     hipLaunchKernelGGL(k_fnewton_solve, dim3(1), dim3(1024), 0, c->stream, L, ldl, c->m, k, X, ldx);
 }
 

@@ -1,4 +1,4 @@
-// Log-weights method, M <= 1024: the dual Newton step's kernels (gfx950).  With w = softmax(g) the weights of the
+// Log-weights method, M <= 1024 (over row panels: M <= 4096): the dual Newton step's kernels (gfx950).  With w = softmax(g) the weights of the
 // kept log-weights point, Y' = Y - centre, grad the point's gradient:
 //   G'     = sum_j w_j Y'_j Y'_j^T
 //   C      = G' - ybar' ybar'^T                          the covariance of the observables under the weights
@@ -24,6 +24,11 @@ __global__ __launch_bounds__(256, 1) void k_logw_gram(FGramArgs q) { fgram_pass<
 // 16 f32 accumulators where k_forces_gram_bf16 has 32: 236 VGPRs, no AGPRs, no scratch -- two waves per SIMD (with bounds of
 // one wave the compiler takes 172 VGPRs + 64 AGPRs, runs two all the same, and is no faster: DESIGN 6k)
 __global__ __launch_bounds__(256, 2) void k_logw_gram_bf16(FGramArgs q) { fgram16_pass<LogwGramPoint<1>>(q); }
+
+// 1024 < M <= 4096: the same two passes with a wave's two slices taken from their row panels' copies
+// (FGramPanelArgs); the panels' pointers, strides and chunk offsets are wave-uniform and live in scalar registers
+__global__ __launch_bounds__(256, 1) void k_logw_gram_panels(FGramPanelArgs q) { fgram_pass<LogwGramPoint<4>>(q); }
+__global__ __launch_bounds__(256, 2) void k_logw_gram_bf16_panels(FGramPanelArgs q) { fgram16_pass<LogwGramPoint<1>>(q); }
 
 // The rank correction and the affine model's scales on the lower triangle, mirrored; the blocks of tile column 0 also leave
 // -b for the solve.  16 x 16 threads per block, blocks above the diagonal leave.
@@ -154,8 +159,12 @@ GramPlan logw_gram_plan(const bioen_hip_ctx* c) { return gram_plan(c, 1, 8, kLog
 
 void launch_logw_gram(bioen_hip_ctx* c, const GramPlan& p, double* buf, const double* e, const double* grad,
                       const double* pscal, const double* ybar, double* negb, bool bf16) {
-    hipLaunchKernelGGL(bf16 ? k_logw_gram_bf16 : k_logw_gram, dim3(fgram_blocks(p)), dim3(256), 0, c->stream,
-                       fgram_args(c, p, buf, e, pscal, grad));
+    if (paneled(c))
+        hipLaunchKernelGGL(bf16 ? k_logw_gram_bf16_panels : k_logw_gram_panels, dim3(fgram_blocks(p)), dim3(256), 0, c->stream,
+                           fgram_panel_args(c, p, buf, e, pscal, grad));
+    else
+        hipLaunchKernelGGL(bf16 ? k_logw_gram_bf16 : k_logw_gram, dim3(fgram_blocks(p)), dim3(256), 0, c->stream,
+                           fgram_args(c, p, buf, e, pscal, grad));
     launch_fgram_sum_sets(c, buf, p.set_stride, c->vr, p.gs);
     const double* sum = buf + (size_t)p.nsets * p.set_stride;
     const int tb = (c->m + 15) / 16;

@@ -417,6 +417,26 @@ def bioen_opt_lbfgs_forces(forces, w0, yTilde, YTilde, theta, params):
     return res, info.fmin
 
 
+class _dense_panels(object):
+    """``with _dense_panels(ctx):`` -- the dual Newton calls of this module beyond 1024 observables: the context's switch
+    (Context.set_dense_panels) is on inside the block and back as it was afterwards, so a context a caller holds
+    (``optimize.resident``) is left as the caller set it.  M <= 1024 needs no switch and none is touched."""
+
+    def __init__(self, ctx):
+        self.ctx, self.was = ctx, None
+
+    def __enter__(self):
+        if self.ctx.m > 1024 and not self.ctx.dense_panels:
+            self.was = False
+            self.ctx.set_dense_panels(True)
+        return self.ctx
+
+    def __exit__(self, *exc):
+        if self.was is not None and getattr(self.ctx, "_h", None):
+            self.ctx.set_dense_panels(self.was)
+        return False
+
+
 def bioen_opt_dual_newton_logw(g, G, yTilde, YTilde, theta, params):
     """-> (gopt[n], fmin): the device-resident dual Newton minimizer of the log-weights method
     (Context.opt_dual_newton_logw).  Status 0 returns; every other status raises RuntimeError with the return code, as
@@ -424,8 +444,9 @@ def bioen_opt_dual_newton_logw(g, G, yTilde, YTilde, theta, params):
     global last_opt_info
     ctx, cached = _context_for(yTilde, YTilde)
     try:
-        res = ctx.opt_dual_newton_logw(np.asarray(g, dtype=np.float64).reshape(-1),
-                                       np.asarray(G, dtype=np.float64).reshape(-1), theta, params["params"])
+        with _dense_panels(ctx):
+            res = ctx.opt_dual_newton_logw(np.asarray(g, dtype=np.float64).reshape(-1),
+                                           np.asarray(G, dtype=np.float64).reshape(-1), theta, params["params"])
     finally:
         _release(ctx, cached)
     last_opt_info = res
@@ -447,8 +468,9 @@ def bioen_opt_dual_newton_logw_series(g, G, yTilde, YTilde, thetas, params):
         raise RuntimeError("dual_newton:series=" + mode + " not recognized (valid values = 'warm', 'cold')")
     ctx, cached = _context_for(yTilde, YTilde)
     try:
-        res = ctx.opt_dual_newton_logw_series([float(t) for t in thetas], np.asarray(g, dtype=np.float64).reshape(-1),
-                                              np.asarray(G, dtype=np.float64).reshape(-1), p, warm=(mode == "warm"))
+        with _dense_panels(ctx):
+            res = ctx.opt_dual_newton_logw_series([float(t) for t in thetas], np.asarray(g, dtype=np.float64).reshape(-1),
+                                                  np.asarray(G, dtype=np.float64).reshape(-1), p, warm=(mode == "warm"))
     finally:
         _release(ctx, cached)
     last_opt_info = res

@@ -702,7 +702,8 @@ int bioen_laplace_forces(bioen_hip_ctx* ctx, const double* forces, const double*
  * is formed, factorised (FP64 Cholesky) and solved in device memory, and the covariance of the observables under the
  * refined weights it is built on.  DESIGN section 6j.
  *
- * Both entries are refused with BIOEN_HIP_ESTATE, each case with a message of its own, on m > 1024 (row panels), on contexts
+ * Both entries are refused with BIOEN_HIP_ESTATE, each case with a message of its own, on m > 1024 (row panels; up to 4096
+ * rows are served after bioen_hip_ctx_set_dense_panels, at the end of this header), on contexts
  * without the strip copies, on the reduced-storage experiment's copies and on structure-sharded contexts. ---- */
 
 /* C = sum_j w_j (y_j - ybar)(y_j - ybar)^T, w = softmax(g): the covariance of the (affine model: effective) observables
@@ -836,6 +837,18 @@ int bioen_logwn_profile_series(bioen_hip_ctx* ctx, const double* g0, const doubl
                                const bioen_logwn_config* config, int source, int warm, const double* row_offset,
                                const int* group, int ngroups, double* gopt, double* scales, double* chi2, double* kl,
                                bioen_logwn_series_result* results);
+
+/* ---- log-weights method: the dual Newton beyond 1024 observables, over the row panels of the matrix.  DESIGN section 6n.
+ * A setting of the context, off by default: with it, bioen_logwn_cov, bioen_logwn_cov_bf16, bioen_logwn_opt and
+ * bioen_logwn_series serve 1024 < m <= 4096 on contexts whose row panels' strip copies are resident (not BIOEN_HIP_PANELS=0,
+ * not the streaming fallback); beyond 4096 rows they answer BIOEN_HIP_ESTATE, naming 4096.  Every other dense entry
+ * (bioen_logwn_laplace, bioen_logwn_profile_series, the forces method's), structure-sharded contexts and the
+ * reduced-storage copies are refused in their present words, setting or not.  m <= 1024 is served as before either way.
+ * The pass's buffer grows with m^2: (sets + 1) x (m / 64)(m / 64 + 1) / 2 sub-tiles of 32 KiB (sets: the context's
+ * canonical segments, 8 unless BIOEN_HIP_SEGMENTS says otherwise, x their groups) -- 68 MB a set at 4096 rows, 0.6 GB in
+ * all -- plus C; the factor's buffer holds 2 m^2 doubles (bioen_hip_ctx_footprint: bits 10 and 8).
+ * on: 0 or 1 (BIOEN_HIP_EINVAL otherwise).  Keeps the point and a session; no device work. ---- */
+int bioen_hip_ctx_set_dense_panels(bioen_hip_ctx* ctx, int on);
 
 #ifdef __cplusplus
 }
